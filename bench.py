@@ -9,9 +9,12 @@ Adagrad, batch 4096 per GPU, Criteo Kaggle field cardinalities) — on
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 bench.py --gpus N ...
 
-Rank 0 prints one JSON line; at the default --amp native it carries BOTH the
+Rank 0 prints one JSON line. A plain run measures the headline only; with
+--full (at the default --amp native) the line carries BOTH the
 bf16-resident-MLP headline and a matched-precision all-fp32 number
 ("matched_precision", measured back-to-back in the same process).
+--dump-outputs DIR writes, as DIR/*.npy, what the timed step computes for the
+last timed batch from the seeded start state (see replay_last_step).
 Baseline: the reference's published DeepFM dim9 throughput on 8x Tesla T4
 (BASELINE.md): 293/458/727/935 k samples/s at 1/2/4/8 GPUs.
 
@@ -45,6 +48,12 @@ import torch.distributed as dist
 BASELINE_SAMPLES_PER_SEC = {1: 293_000.0, 2: 458_000.0, 4: 727_000.0,
                             8: 935_000.0}
 
+DUMP_ROWS_MAX_BYTES = 32 << 20  # --dump-outputs: cap on embedding_rows.npy
+# --dump-outputs: steps from the seeded state. Two, so that the dumped step
+# also reflects gradient magnitudes (Adagrad's first update is +-lr whatever
+# the magnitude), yet rounding has had one step to grow, not thousands.
+DUMP_STEPS = 2
+
 
 def build_model(args, embed, amp_mode, device, on_gpu):
     from openembedding_amd.models import MODELS
@@ -65,11 +74,11 @@ def build_model(args, embed, amp_mode, device, on_gpu):
     return model, opt
 
 
-def measure(args, embed, amp_mode, steps, warmup, pool, device, world, rank):
-    """Build the model at ``amp_mode`` and time ``steps`` steps. Returns a
-    dict with value/ms_per_step/graph/prefetch."""
+def make_step(model, opt, amp_mode, device, keep=None):
+    """The train step that the benchmark times (eagerly, or captured once in
+    a hipGraph and replayed). ``keep``: a dict that receives the step's
+    logits and loss, detached."""
     on_gpu = device.type == "cuda"
-    model, opt = build_model(args, embed, amp_mode, device, on_gpu)
     # fused 2-kernel BCE on GPU (torch's spends ~5 launches/step in the
     # captured graph), plain torch BCE elsewhere
     from openembedding_amd.ops.dispatch import bce_with_logits as lossf
@@ -89,7 +98,60 @@ def measure(args, embed, amp_mode, steps, warmup, pool, device, world, rank):
         loss = lossf(out.float(), labels)
         loss.backward(gradient=seed_one)
         opt.step()
+        if keep is not None:
+            keep["out"], keep["loss"] = out.detach(), loss.detach()
         return loss
+
+    return run_step
+
+
+def replay_last_step(args, embed, amp_mode, device, batch):
+    """--dump-outputs: what the timed step computes for the last timed
+    batch from the seeded start state, as float32 numpy arrays.
+
+    The state after N timed steps is not a function of the inputs: the step
+    sums gradients with float atomics, rounding differs run to run, and
+    Adagrad on a memorised pool amplifies it step by step (measured: logits
+    apart by 0.75 after 220 steps of one build). So the dump pins the state
+    too: a second model built from the same seeds — bit-identical to the one
+    the timed run started from — takes DUMP_STEPS steps of the timed step
+    function on that batch, and the last of them is written out: its logits
+    and loss, and the state it left (dense parameters, and the embedding
+    rows of the batch's keys)."""
+    model, opt = build_model(args, embed, amp_mode, device,
+                             device.type == "cuda")
+    last = {}
+    run_step = make_step(model, opt, amp_mode, device, keep=last)
+    for _ in range(DUMP_STEPS):
+        run_step(*batch)
+    _, sparse, _ = batch
+    emb = model.embedding
+    # keep the dump small: past 32 MB of rows, a fixed seeded sample of the
+    # batch's samples stands for the whole
+    row_bytes = sparse.shape[1] * emb.embedding_dim * 4
+    if sparse.shape[0] * row_bytes > DUMP_ROWS_MAX_BYTES:
+        g = torch.Generator(device="cpu").manual_seed(99)
+        pick = torch.randperm(sparse.shape[0], generator=g)
+        pick = pick[:DUMP_ROWS_MAX_BYTES // row_bytes].sort().values
+        sparse = sparse[pick.to(sparse.device)]
+    if emb.variable is not None:
+        keys = sparse.to(torch.int64) + emb.field_offsets
+        rows = emb.variable.sparse_read(keys)  # collective at world>1
+    else:
+        rows = emb.dense(sparse.to(torch.int64) + emb.field_offsets)
+    dense = [p.detach().float().flatten() for p in model.parameters()
+             if p.numel() > 0]
+    outs = {"logits": last["out"], "loss": last["loss"].reshape(1),
+            "dense_params": torch.cat(dense), "embedding_rows": rows}
+    return {k: v.detach().float().cpu().numpy() for k, v in outs.items()}
+
+
+def measure(args, embed, amp_mode, steps, warmup, pool, device, world, rank):
+    """Build the model at ``amp_mode`` and time ``steps`` steps. Returns a
+    dict with value/ms_per_step/graph/prefetch."""
+    on_gpu = device.type == "cuda"
+    model, opt = build_model(args, embed, amp_mode, device, on_gpu)
+    run_step = make_step(model, opt, amp_mode, device)
 
     # hipGraph capture: single-GPU since round 1; multi-rank too now that
     # the padded all-to-all route is sync-free (RCCL collectives capture
@@ -220,8 +282,9 @@ def main():
                         "bf16-resident MLP weights + the fused single-kernel "
                         "MLP, fp32 master/accumulators in the flat optimizer. "
                         "Embeddings, FM math, loss, optimizer state fp32. "
-                        "The default also re-measures all-fp32 and reports "
-                        "it as matched_precision in the same JSON line.")
+                        "With --full the default also re-measures all-fp32 "
+                        "and reports it as matched_precision in the same "
+                        "JSON line.")
     p.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                    help="capture the train step in a hipGraph")
     p.add_argument("--hash", action="store_true",
@@ -231,8 +294,18 @@ def main():
                    help="force the pulling() prefetch pipeline (default: "
                         "automatic at world>1 when the step is not "
                         "graph-captured)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (the "
+                        "matched-precision all-fp32 re-measurement); a plain "
+                        "run times the headline only")
     p.add_argument("--no-matched-precision", action="store_true",
-                   help="skip the secondary all-fp32 measurement")
+                   help="with --full: skip the secondary all-fp32 measurement")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed step "
+                        "computes for the last timed batch, taken from the "
+                        "seeded start state so that runs repeat (logits, "
+                        "loss, dense parameters, the embedding rows of its "
+                        "keys), as DIR/<name>.npy")
     p.add_argument("--cache-mb", type=int, default=0,
                    help="capacity tier: device row-cache budget in MB, cold "
                         "rows spill to host DRAM (implies --hash)")
@@ -264,10 +337,18 @@ def main():
     amp_mode = args.amp
     main_res = measure(args, embed, amp_mode, args.steps, args.warmup, pool,
                        device, world, rank)
+    if args.dump_outputs is not None:
+        last_batch = pool[(args.warmup + args.steps - 1) % len(pool)]
+        outputs = replay_last_step(args, embed, amp_mode, device, last_batch)
+        if rank == 0:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
 
     matched = None
-    if (amp_mode == "native" and on_gpu and not args.no_matched_precision
-            and args.model != "lr"):
+    if (args.full and amp_mode == "native" and on_gpu
+            and not args.no_matched_precision and args.model != "lr"):
         msteps = max(10, args.steps // 4)
         mres = measure(args, embed, "off", msteps, max(5, args.warmup // 2),
                        pool, device, world, rank)

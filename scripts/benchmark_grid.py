@@ -19,8 +19,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def run_cell(model, dim, n_gpus, steps, warmup, batch):
+    # --full: each row also carries the matched-precision fp32 measurement
     args = [f"--model={model}", f"--dim={dim}", f"--gpus={n_gpus}",
-            f"--steps={steps}", f"--warmup={warmup}", f"--batch={batch}"]
+            f"--steps={steps}", f"--warmup={warmup}", f"--batch={batch}",
+            "--full"]
     if n_gpus == 1:
         cmd = [sys.executable, "bench.py"] + args
     else:
