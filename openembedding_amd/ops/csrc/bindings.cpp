@@ -53,7 +53,7 @@ void emb_mlp3_bias_bwd(const float*, const void*, const void*, const void*,
                        void*, void*, int, int, hipStream_t_);
 void emb_mlp3_wgrad(const void*, const void*, const void*, const void*,
                     const void*, const void*, long, long, long, long,
-                    float*, void*, void*, void*, float*, hipStream_t_);
+                    float*, void*, void*, void*, float*, long, hipStream_t_);
 void emb_mlp3_pack(const void*, void*, long, long, long, long, int,
                    const void*, void*, long, long, long, long, int,
                    const void*, void*, long, long, long, long, int,
@@ -94,11 +94,11 @@ void emb_cin_dx(const float*, const void*, const float*, const float*,
 void emb_mlp3_fwd(const void*, long, long, const void*, const void*,
                   const void*, const void*, const void*, const void*,
                   const void*, const void*, const float*, long, long, void*,
-                  void*, void*, float*, hipStream_t_);
+                  void*, void*, float*, int, hipStream_t_);
 void emb_mlp3_bwd(const float*, long, long, const void*, const void*,
                   const void*, const void*, const void*, const void*,
                   const void*, long, long, void*, void*, void*, void*,
-                  float*, hipStream_t_);
+                  float*, int, hipStream_t_);
 }
 
 namespace {
@@ -632,7 +632,7 @@ std::tuple<torch::Tensor, torch::Tensor> cin_dx(
 void mlp3_wgrad(torch::Tensor dz1, torch::Tensor dz2, torch::Tensor dz3,
                 torch::Tensor x0, torch::Tensor a1, torch::Tensor a2,
                 torch::Tensor scratch, torch::Tensor dw1, torch::Tensor dw2,
-                torch::Tensor dw3, OptTensor bias_scratch) {
+                torch::Tensor dw3, OptTensor bias_scratch, long m_split) {
     // bias_scratch ([4H+1] fp32, the bias pass scratch): when given, the
     // kernel also accumulates the three dz column sums (bias grads) from
     // its LDS-staged tiles into segments 0/H/2H
@@ -644,6 +644,13 @@ void mlp3_wgrad(torch::Tensor dz1, torch::Tensor dz2, torch::Tensor dz3,
     long M = dz1.size(0), H = dz1.size(1), K0p = x0.size(1);
     long K0 = dw1.size(1);
     TORCH_CHECK(M % 32 == 0, "mlp3_wgrad: M must be x32");
+    // 16-byte row pieces: every operand row must start 16-byte aligned
+    TORCH_CHECK(H % 8 == 0 && K0p % 8 == 0 && a1.size(1) == H
+                && a2.size(1) == H, "mlp3_wgrad: H, K0p must be x8");
+    for (const torch::Tensor* t : {&dz1, &dz2, &dz3, &x0, &a1, &a2})
+        TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                    "mlp3_wgrad: operands must be 16-byte aligned");
+    TORCH_CHECK(m_split >= 0 && m_split <= 64, "mlp3_wgrad: m_split");
     TORCH_CHECK(scratch.numel() >= H * K0p + 2 * H * H
                 && dw1.size(0) == H && K0 <= K0p && dw2.numel() == H * H
                 && dw3.numel() == H * H
@@ -661,7 +668,8 @@ void mlp3_wgrad(torch::Tensor dz1, torch::Tensor dz2, torch::Tensor dz3,
     emb_mlp3_wgrad(dz1.data_ptr(), dz2.data_ptr(), dz3.data_ptr(),
                    x0.data_ptr(), a1.data_ptr(), a2.data_ptr(), M, H, K0p,
                    K0, scratch.data_ptr<float>(), dw1.data_ptr(),
-                   dw2.data_ptr(), dw3.data_ptr(), bptr, cur_stream());
+                   dw2.data_ptr(), dw3.data_ptr(), bptr, m_split,
+                   cur_stream());
 }
 
 void mlp3_pack(torch::Tensor s1, torch::Tensor d1, bool t1,
@@ -726,7 +734,9 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 mlp3_fwd(torch::Tensor x0, torch::Tensor w1, torch::Tensor b1,
          torch::Tensor w2, torch::Tensor b2, torch::Tensor w3,
          torch::Tensor b3, torch::Tensor w4, torch::Tensor b4,
-         c10::optional<torch::Tensor> partial) {
+         c10::optional<torch::Tensor> partial, long bm) {
+    // bm: rows per block, 0 = the launcher's choice; 16/32/64 force one
+    // kernel variant (tests)
     CHECK_GPU(x0); CHECK_CONT(x0);
     TORCH_CHECK(x0.dtype() == torch::kBFloat16, "mlp3_fwd: x0 must be bf16");
     const c10::cuda::CUDAGuard guard(x0.device());
@@ -737,6 +747,9 @@ mlp3_fwd(torch::Tensor x0, torch::Tensor w1, torch::Tensor b1,
                 "mlp3_fwd: padded K dims must be x32");
     TORCH_CHECK(w1.size(1) == K0p && w2.size(0) == H && w3.size(0) == H
                 && w3.size(1) == Hp && w4.numel() == H);
+    TORCH_CHECK(bm == 0 || bm == 16 || ((bm == 32 || bm == 64)
+                                        && K0p <= 416),
+                "mlp3_fwd: bm must be 0, 16, 32 or 64 (32/64: K0p <= 416)");
     auto a1 = torch::empty({M, H}, x0.options());
     auto a2 = torch::empty({M, H}, x0.options());
     auto a3 = torch::empty({M, H}, x0.options());
@@ -752,14 +765,15 @@ mlp3_fwd(torch::Tensor x0, torch::Tensor w1, torch::Tensor b1,
                  w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
                  w3.data_ptr(), b3.data_ptr(), w4.data_ptr(), b4.data_ptr(),
                  pp, H, Hp, a1.data_ptr(), a2.data_ptr(), a3.data_ptr(),
-                 out.data_ptr<float>(), cur_stream());
+                 out.data_ptr<float>(), (int)bm, cur_stream());
     return {out, a1, a2, a3};
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 mlp3_bwd(torch::Tensor dout, torch::Tensor a1, torch::Tensor a2,
          torch::Tensor a3, torch::Tensor w4, torch::Tensor w3t,
-         torch::Tensor w2t, torch::Tensor w1t, OptTensor bias_scratch) {
+         torch::Tensor w2t, torch::Tensor w1t, OptTensor bias_scratch,
+         long bm) {
     // bias_scratch ([4H+1] fp32): when given, the dz3 assembly loop also
     // accumulates dw4 (dout.a3 column sums) and db4 into segments 3H/4H
     CHECK_GPU(dout); CHECK_CONT(dout); CHECK_CONT(w3t); CHECK_CONT(w2t);
@@ -768,6 +782,10 @@ mlp3_bwd(torch::Tensor dout, torch::Tensor a1, torch::Tensor a2,
     long M = a1.size(0), H = a1.size(1), K0p = w1t.size(0);
     long Hp = w3t.size(1);
     TORCH_CHECK(Hp % 32 == 0 && w2t.size(1) == Hp && w1t.size(1) == Hp);
+    TORCH_CHECK(H % 16 == 0 && H <= 416 && K0p % 16 == 0,
+                "mlp3_bwd: H must be <=416, x16");
+    TORCH_CHECK(bm == 0 || bm == 16 || bm == 32 || bm == 64,
+                "mlp3_bwd: bm must be 0, 16, 32 or 64");
     auto dz1 = torch::empty_like(a1);
     auto dz2 = torch::empty_like(a2);
     auto dz3 = torch::empty_like(a3);
@@ -784,7 +802,7 @@ mlp3_bwd(torch::Tensor dout, torch::Tensor a1, torch::Tensor a2,
                  a2.data_ptr(), a3.data_ptr(), w4.data_ptr(), w3t.data_ptr(),
                  w2t.data_ptr(), w1t.data_ptr(), H, Hp, dz1.data_ptr(),
                  dz2.data_ptr(), dz3.data_ptr(), dx0.data_ptr(), bptr,
-                 cur_stream());
+                 (int)bm, cur_stream());
     return {dx0, dz1, dz2, dz3};
 }
 
@@ -835,18 +853,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("dout"), pybind11::arg("a1"), pybind11::arg("a2"),
           pybind11::arg("a3"), pybind11::arg("w4"), pybind11::arg("w3t"),
           pybind11::arg("w2t"), pybind11::arg("w1t"),
-          pybind11::arg("bias_scratch") = pybind11::none());
+          pybind11::arg("bias_scratch") = pybind11::none(),
+          pybind11::arg("bm") = 0);
     m.def("mlp3_pack", &mlp3_pack,
           "refresh three padded (or transposed) weight copies in one "
           "launch");
     m.def("mlp3_fwd", &mlp3_fwd,
-          "fused 3-hidden-layer MLP forward (bf16 MFMA, bias+ReLU fused)");
+          "fused 3-hidden-layer MLP forward (bf16 MFMA, bias+ReLU fused)",
+          pybind11::arg("x0"), pybind11::arg("w1"), pybind11::arg("b1"),
+          pybind11::arg("w2"), pybind11::arg("b2"), pybind11::arg("w3"),
+          pybind11::arg("b3"), pybind11::arg("w4"), pybind11::arg("b4"),
+          pybind11::arg("partial"), pybind11::arg("bm") = 0);
     m.def("mlp3_wgrad", &mlp3_wgrad,
           pybind11::arg("dz1"), pybind11::arg("dz2"), pybind11::arg("dz3"),
           pybind11::arg("x0"), pybind11::arg("a1"), pybind11::arg("a2"),
           pybind11::arg("scratch"), pybind11::arg("dw1"),
           pybind11::arg("dw2"), pybind11::arg("dw3"),
           pybind11::arg("bias_scratch") = pybind11::none(),
+          pybind11::arg("m_split") = 0,
           "all three MLP weight grads in one MFMA launch (+= into bf16 "
           "grads via fp32 scratch)");
     m.def("mlp3_bias_bwd", &mlp3_bias_bwd,
