@@ -217,6 +217,19 @@ class HipVariableShard(VariableShard):
                            inverse=inverse, u_dev=u_dev)
         return out, slots
 
+    def pull_pooled_bounded(self, keys_buf: torch.Tensor,
+                            u_dev: torch.Tensor, inverse: torch.Tensor,
+                            offsets: torch.Tensor, mode: int):
+        """Sync-free pooled pull over ragged bags: lookup/insert, lazy init
+        of new rows only (no output), then the pooling kernel reads
+        ``self.weights`` straight through ``slots`` — no [nnz, dim] tensor
+        exists. Returns (out [B, dim], slots, bag_of [nnz])."""
+        slots, new_mask = self._lookup_or_insert(keys_buf, u_dev)
+        self._gather(keys_buf, slots, new_mask, False, u_dev=u_dev)
+        out, bag_of = self.ext.pool_fwd(self.weights, inverse, slots,
+                                        offsets, mode, True)
+        return out, slots, bag_of
+
     def push_slots(self, keys_buf, u_dev, slots, grads, counts) -> None:
         """Queue a bounded pre-reduced block whose table slots are already
         known (saved from the matching pull)."""

@@ -38,6 +38,12 @@ void emb_gather_init(float*, float*, long, long, const i64*,
                      const int*, hipStream_t_);
 void emb_reduce_by_inverse(const i64*, const float*, long, long, float*, u64*,
                            long, hipStream_t_);
+void emb_reduce_bags_by_inverse(const i64*, const float*, long, long,
+                                const int*, const i64*, long, int, float*,
+                                u64*, long, hipStream_t_);
+void emb_pool_fwd(const float*, long, long, const i64*, long, const void*,
+                  int, long, const i64*, long, int, float*, int*,
+                  hipStream_t_);
 void emb_apply_optimizer(int, float*, float*, long, long, const i64*, long,
                          const float*, const u64*, const float*, const int*,
                          hipStream_t_);
@@ -264,6 +270,99 @@ std::tuple<torch::Tensor, torch::Tensor> reduce_by_inverse(
     emb_reduce_by_inverse(inverse.data_ptr<i64>(), grads.data_ptr<float>(), n,
                           dim, ugrads.data_ptr<float>(),
                           (u64*)counts.data_ptr<i64>(), u, cur_stream());
+    return {ugrads, counts};
+}
+
+// ---- multi-hot bags: pooled gather + bag-indirected reduce ------------
+
+// rows [R, dim] f32; inverse (optional: identity) int64 [nnz]; map
+// (optional) int64 or int32 [u], -1 = zero row; offsets int64 [B+1];
+// mode 0 sum / 1 mean / 2 sqrtn. Returns (out [B, dim], bag_of int32
+// [nnz]; empty when !want_bag_of).
+std::tuple<torch::Tensor, torch::Tensor> pool_fwd(
+    torch::Tensor rows, OptTensor inverse, OptTensor map,
+    torch::Tensor offsets, int64_t mode, bool want_bag_of) {
+    CHECK_GPU(rows); CHECK_CONT(rows);
+    CHECK_GPU(offsets); CHECK_CONT(offsets);
+    TORCH_CHECK(rows.dtype() == torch::kFloat32 && rows.dim() == 2,
+                "pool_fwd: rows must be float32 [R, dim]");
+    TORCH_CHECK(offsets.dtype() == torch::kInt64 && offsets.dim() == 1
+                && offsets.numel() >= 1,
+                "pool_fwd: offsets must be int64 [B+1]");
+    TORCH_CHECK(mode >= 0 && mode <= 2, "pool_fwd: bad mode");
+    const void* map_ptr = nullptr;
+    int map_kind = 0;
+    long u = 0;
+    if (map.has_value()) {
+        CHECK_GPU(*map); CHECK_CONT(*map);
+        u = map->numel();
+        if (map->dtype() == torch::kInt64) {
+            map_kind = 1;
+            map_ptr = map->data_ptr<i64>();
+        } else {
+            TORCH_CHECK(map->dtype() == torch::kInt32,
+                        "pool_fwd: map must be int64 or int32");
+            map_kind = 2;
+            map_ptr = map->data_ptr<int>();
+        }
+    }
+    long R = rows.size(0), dim = rows.size(1);
+    long nnz = map_kind ? u : R;
+    const i64* inv_ptr = nullptr;
+    if (inverse.has_value()) {
+        CHECK_GPU(*inverse); CHECK_CONT(*inverse);
+        TORCH_CHECK(inverse->dtype() == torch::kInt64,
+                    "pool_fwd: inverse must be int64");
+        nnz = inverse->numel();
+        inv_ptr = inverse->data_ptr<i64>();
+    }
+    const c10::cuda::CUDAGuard guard(rows.device());
+    long B = offsets.numel() - 1;
+    auto out = torch::empty({B, dim}, rows.options());
+    auto bag_of = torch::empty({want_bag_of ? nnz : 0},
+                               rows.options().dtype(torch::kInt32));
+    emb_pool_fwd(rows.data_ptr<float>(), R, dim, inv_ptr, nnz, map_ptr,
+                 map_kind, u, offsets.data_ptr<i64>(), B, (int)mode,
+                 out.data_ptr<float>(),
+                 want_bag_of ? bag_of.data_ptr<int>() : nullptr,
+                 cur_stream());
+    return {out, bag_of};
+}
+
+// Same (ugrads [u, dim], counts [u]) as reduce_by_inverse over the
+// expanded gradient grad_out[bag_of[e]] * scale[bag_of[e]], without
+// building it; elements with bag_of < 0 are skipped.
+std::tuple<torch::Tensor, torch::Tensor> reduce_bags_by_inverse(
+    torch::Tensor inverse, torch::Tensor grad_out, torch::Tensor bag_of,
+    torch::Tensor offsets, int64_t mode, int64_t u) {
+    CHECK_GPU(grad_out); CHECK_CONT(grad_out);
+    CHECK_GPU(inverse); CHECK_CONT(inverse);
+    CHECK_GPU(bag_of); CHECK_CONT(bag_of);
+    CHECK_GPU(offsets); CHECK_CONT(offsets);
+    TORCH_CHECK(grad_out.dtype() == torch::kFloat32 && grad_out.dim() == 2,
+                "reduce_bags_by_inverse: grad_out must be float32 [B, dim]");
+    TORCH_CHECK(inverse.dtype() == torch::kInt64
+                && bag_of.dtype() == torch::kInt32
+                && offsets.dtype() == torch::kInt64,
+                "reduce_bags_by_inverse dtypes");
+    TORCH_CHECK(bag_of.numel() == inverse.numel(),
+                "reduce_bags_by_inverse: bag_of/inverse length mismatch");
+    TORCH_CHECK(offsets.numel() == grad_out.size(0) + 1,
+                "reduce_bags_by_inverse: offsets must be [B+1]");
+    TORCH_CHECK(mode >= 0 && mode <= 2, "reduce_bags_by_inverse: bad mode");
+    const c10::cuda::CUDAGuard guard(grad_out.device());
+    long n = inverse.numel();
+    long B = grad_out.size(0);
+    long dim = grad_out.size(1);
+    auto ugrads = torch::empty({u, dim}, grad_out.options());
+    auto counts = torch::empty({u}, grad_out.options().dtype(torch::kInt64));
+    emb_reduce_bags_by_inverse(inverse.data_ptr<i64>(),
+                               grad_out.data_ptr<float>(), n, dim,
+                               bag_of.data_ptr<int>(),
+                               offsets.data_ptr<i64>(), B, (int)mode,
+                               ugrads.data_ptr<float>(),
+                               (u64*)counts.data_ptr<i64>(), u,
+                               cur_stream());
     return {ugrads, counts};
 }
 
@@ -823,6 +922,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "row gather with fused lazy init (+ optional duplicate scatter)");
     m.def("reduce_by_inverse", &reduce_by_inverse,
           "grad reduce-by-key with counts (LDS-aggregated)");
+    m.def("pool_fwd", &pool_fwd,
+          "segment-pooled gather (sum/mean/sqrtn) over ragged bags; also "
+          "emits each element's bag for the backward",
+          pybind11::arg("rows"), pybind11::arg("inverse"),
+          pybind11::arg("map"), pybind11::arg("offsets"),
+          pybind11::arg("mode"), pybind11::arg("want_bag_of") = true);
+    m.def("reduce_bags_by_inverse", &reduce_bags_by_inverse,
+          "grad reduce-by-key reading the pooled [B, dim] gradient through "
+          "bag_of (no [nnz, dim] expansion)");
     m.def("apply_optimizer", &apply_optimizer, "fused sparse optimizer step");
     m.def("mask_tail", &mask_tail,
           "zero the garbage tail of a bounded block (enables multi-block "

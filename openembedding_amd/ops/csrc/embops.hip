@@ -493,6 +493,124 @@ __global__ void k_gather_init(float* __restrict__ weights,
     }
 }
 
+// ------------------------------------------------- segment-pooled gather
+// Multi-hot bags (the reference's ragged sparse_read, exb.py:315-321, plus
+// the sum/mean/sqrtn combiner CTR models apply on top): bag b pools the
+// rows of values[offsets[b] .. offsets[b+1]). Pooling inside the gather
+// means no [nnz, dim] tensor is ever written.
+
+enum { POOL_SUM = 0, POOL_MEAN = 1, POOL_SQRTN = 2 };
+
+// every offsets value is clamped before use: a malformed offsets tensor
+// can give wrong bags but never an out-of-range read
+DEV long pool_clamp(i64 v, long nnz) {
+    return v < 0 ? 0 : (v > (i64)nnz ? nnz : (long)v);
+}
+
+DEV float pool_scale(int mode, long len) {
+    if (len <= 0) return 0.0f;
+    if (mode == POOL_MEAN) return 1.0f / (float)len;
+    if (mode == POOL_SQRTN) return 1.0f / sqrtf((float)len);
+    return 1.0f;
+}
+
+// One G-lane group per bag, lanes over columns, PF_CF column fragments per
+// lane held in registers (dim <= PF_CF*G in one pass, wider rows loop).
+// The index chain (inverse -> map -> row) is resolved lane-parallel: lane l
+// of the group resolves element j0+l, so G elements cost ONE pass of the
+// dependent chain (two coalesced-index loads), and the next G elements'
+// chain is issued before this chunk's row reads. Rows are then broadcast
+// through __shfl and read PF_ILP at a time — the latency plan of
+// k_gather_init, which matters most for the long bags of a long-tailed
+// length distribution (one group walks its whole bag). Rows are added in
+// element order with plain adds, so the result is bitwise reproducible
+// (no atomics).
+// ``inverse`` null = identity; ``map`` null = inverse indexes rows
+// directly; a mapped row < 0 (or out of range) contributes zero.
+// ``bag_of`` (optional, [nnz]) receives each element's bag, -1 for the
+// tail at or beyond offsets[B] — the backward reduce reads it.
+// PF_CF * PF_ILP row values are in flight per lane; the launcher trades
+// column fragments for elements so narrow rows get the deeper element
+// preload (a 16-element chunk of a dim <= 16 bag is ONE load latency).
+
+// row of ``rows`` that element j reads, -1 = contributes zero (j outside
+// the bag, an index outside its table, or a mapped miss)
+template <typename MapT>
+DEV long pool_row(long j, long e, const i64* __restrict__ inverse,
+                  const MapT* __restrict__ map, long nidx, long R) {
+    if (j >= e) return -1;
+    long uid = inverse ? (long)inverse[j] : j;
+    if (uid < 0 || uid >= nidx) return -1;
+    long row = map ? (long)map[uid] : uid;
+    return (row >= 0 && row < R) ? row : -1;
+}
+
+template <int G, int PF_CF, int PF_ILP, typename MapT>
+__global__ void k_pool_fwd(const float* __restrict__ rows, long R, long dim,
+                           const i64* __restrict__ inverse, long nnz,
+                           const MapT* __restrict__ map, long u,
+                           const i64* __restrict__ offsets, long B, int mode,
+                           float* __restrict__ out,
+                           int* __restrict__ bag_of) {
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (bag_of) {
+        const long nthreads = (long)gridDim.x * blockDim.x;
+        for (long j = pool_clamp(offsets[B], nnz) + tid; j < nnz;
+             j += nthreads)
+            bag_of[j] = -1;
+    }
+    const long b = tid / G;
+    const int lane = threadIdx.x % G;
+    if (b >= B) return;
+    const long s = pool_clamp(offsets[b], nnz);
+    long e = pool_clamp(offsets[b + 1], nnz);
+    if (e < s) e = s;
+    const float scale = pool_scale(mode, e - s);
+    const long nidx = map ? u : R;   // valid range of an inverse value
+    for (long c0 = 0; c0 < dim; c0 += (long)G * PF_CF) {
+        float acc[PF_CF];
+        #pragma unroll
+        for (int k = 0; k < PF_CF; ++k) acc[k] = 0.0f;
+        long myrow = pool_row(s + lane, e, inverse, map, nidx, R);
+        for (long j0 = s; j0 < e; j0 += G) {
+            const long nextrow = pool_row(j0 + G + lane, e, inverse, map,
+                                          nidx, R);
+            const int cnt = (int)((e - j0) < G ? (e - j0) : G);
+            for (int t0 = 0; t0 < cnt; t0 += PF_ILP) {
+                long row[PF_ILP];
+                #pragma unroll
+                for (int t = 0; t < PF_ILP; ++t)    // t0 + t < G always
+                    row[t] = __shfl(myrow, t0 + t, G);
+                float v[PF_ILP][PF_CF];
+                #pragma unroll
+                for (int t = 0; t < PF_ILP; ++t) {
+                    #pragma unroll
+                    for (int k = 0; k < PF_CF; ++k) {
+                        long c = c0 + lane + (long)k * G;
+                        v[t][k] = (row[t] >= 0 && c < dim)
+                                      ? rows[(u64)row[t] * dim + c] : 0.0f;
+                    }
+                }
+                #pragma unroll
+                for (int t = 0; t < PF_ILP; ++t) {
+                    if (t0 + t < cnt) {
+                        #pragma unroll
+                        for (int k = 0; k < PF_CF; ++k) acc[k] += v[t][k];
+                    }
+                }
+            }
+            myrow = nextrow;
+        }
+        #pragma unroll
+        for (int k = 0; k < PF_CF; ++k) {
+            long c = c0 + lane + (long)k * G;
+            if (c < dim) out[(u64)b * dim + c] = acc[k] * scale;
+        }
+    }
+    if (bag_of)
+        for (long j = s + lane; j < e; j += G) bag_of[j] = (int)b;
+}
+
 // -------------------------------------------------------- reduce-by-inverse
 // Hot rows (small-vocab fields) make direct global atomics serialize; for
 // dim <= 32 gradients+counts are pre-aggregated in an LDS hash per block
@@ -504,12 +622,34 @@ __global__ void k_gather_init(float* __restrict__ weights,
 // version did `dim` serial LDS atomics per element with strided reads —
 // 112us avg in the DeepFM profile; this shape removes both problems).
 // Lane 0 of the group probes the LDS hash and broadcasts the slot.
-template <int H, int G, int GF = 4>
+//
+// BAG = true is the pooled (multi-hot) backward: ``grads`` is then the
+// [B, dim] gradient of the pooled output and element e reads row
+// bag_of[e] of it, scaled by its bag's combiner scale — the [nnz, dim]
+// expansion autograd would build is never materialised. Elements whose
+// bag_of is outside [0, B) (the fixed-capacity tail) add neither gradient
+// nor count. BAG = false compiles to the plain kernel.
+
+// row of the pooled gradient + scale for an element of bag ``bag``, or -1
+// to skip it
+DEV long reduce_src(int bag, long n, const i64* __restrict__ offsets,
+                    long B, int mode, float& scale) {
+    if (bag < 0 || bag >= B) return -1;
+    if (mode != POOL_SUM)
+        scale = pool_scale(mode, pool_clamp(offsets[bag + 1], n)
+                                     - pool_clamp(offsets[bag], n));
+    return bag;
+}
+
+template <int H, int G, int GF = 4, bool BAG = false>
 __global__ void k_reduce_lds(const i64* __restrict__ inverse,
                              const float* __restrict__ grads,
                              long n, long dim,
                              float* __restrict__ ugrads,
-                             u64* __restrict__ counts) {
+                             u64* __restrict__ counts,
+                             const int* __restrict__ bag_of,
+                             const i64* __restrict__ offsets,
+                             long B, int mode) {
     extern __shared__ char smem[];
     int* luid = (int*)smem;
     int* lcnt = (int*)(smem + H * 4);
@@ -536,15 +676,46 @@ __global__ void k_reduce_lds(const i64* __restrict__ inverse,
     }
     float gfrag[2][GF];  // up to GF grad values per lane (dim <= GF*G)
     const int nj = (int)((dim + G - 1) / G);
-    #pragma unroll
-    for (int j = 0; j < GF; ++j)
-        gfrag[0][j] = (j < nj && base < n && lane + j * G < dim)
-                          ? grads[(u64)base * dim + lane + j * G] : 0.0f;
+    // BAG only: every element's bag preloaded like its uid, then the row
+    // of the pooled gradient (-1 = skip the element) and the combiner
+    // scale of the two staged elements
+    int bags[BAG ? G : 1];
+    long gsrc[2] = {-1, -1};
+    float gscale[2] = {1.0f, 1.0f};
+    if constexpr (BAG) {
+        #pragma unroll
+        for (int t = 0; t < G; ++t) {
+            long e = base + t;
+            bags[t] = (e < n) ? bag_of[e] : -1;
+        }
+        gsrc[0] = reduce_src(bags[0], n, offsets, B, mode, gscale[0]);
+        #pragma unroll
+        for (int j = 0; j < GF; ++j)
+            gfrag[0][j] = (j < nj && gsrc[0] >= 0 && lane + j * G < dim)
+                ? grads[(u64)gsrc[0] * dim + lane + j * G] : 0.0f;
+    } else {
+        #pragma unroll
+        for (int j = 0; j < GF; ++j)
+            gfrag[0][j] = (j < nj && base < n && lane + j * G < dim)
+                              ? grads[(u64)base * dim + lane + j * G] : 0.0f;
+    }
     for (int t = 0; t < G; ++t) {
         long e = base + t;
         if (e >= n) break;
         long en = base + t + 1;
-        if (en < n) {
+        if constexpr (BAG) {
+            if (t + 1 < G) {
+                const int nb = (t + 1) & 1;
+                gsrc[nb] = reduce_src(bags[t + 1], n, offsets, B, mode,
+                                      gscale[nb]);
+                #pragma unroll
+                for (int j = 0; j < GF; ++j)
+                    gfrag[nb][j] = (j < nj && gsrc[nb] >= 0
+                                    && lane + j * G < dim)
+                        ? grads[(u64)gsrc[nb] * dim + lane + j * G] : 0.0f;
+            }
+            if (gsrc[t & 1] < 0) continue;   // tail element: no-op
+        } else if (en < n) {
             #pragma unroll
             for (int j = 0; j < GF; ++j)
                 gfrag[(t + 1) & 1][j] = (j < nj && lane + j * G < dim)
@@ -568,7 +739,9 @@ __global__ void k_reduce_lds(const i64* __restrict__ inverse,
         #pragma unroll
         for (int j = 0; j < GF; ++j)
             if (j < nj && lane + j * G < dim)
-                atomicAdd(&dstb[lane + j * G], gfrag[t & 1][j]);
+                atomicAdd(&dstb[lane + j * G],
+                          BAG ? gfrag[t & 1][j] * gscale[t & 1]
+                              : gfrag[t & 1][j]);
     }
     __syncthreads();
     for (int h = group; h < H; h += (int)(blockDim.x / G)) {
@@ -581,20 +754,35 @@ __global__ void k_reduce_lds(const i64* __restrict__ inverse,
     }
 }
 
+template <bool BAG = false>
 __global__ void k_reduce_grads(const i64* __restrict__ inverse,
                                const float* __restrict__ grads,
                                long n, long dim,
-                               float* __restrict__ ugrads) {
+                               float* __restrict__ ugrads,
+                               const int* __restrict__ bag_of,
+                               const i64* __restrict__ offsets,
+                               long B, int mode) {
     long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n * dim) return;
     long i = e / dim, j = e % dim;
-    atomicAdd(&ugrads[inverse[i] * dim + j], grads[e]);
+    if (BAG) {
+        float scale = 1.0f;
+        long src = reduce_src(bag_of[i], n, offsets, B, mode, scale);
+        if (src < 0) return;
+        atomicAdd(&ugrads[inverse[i] * dim + j],
+                  grads[(u64)src * dim + j] * scale);
+    } else {
+        atomicAdd(&ugrads[inverse[i] * dim + j], grads[e]);
+    }
 }
 
+template <bool BAG = false>
 __global__ void k_reduce_counts(const i64* __restrict__ inverse, long n,
-                                u64* __restrict__ counts) {
+                                u64* __restrict__ counts,
+                                const int* __restrict__ bag_of, long B) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (BAG && (bag_of[i] < 0 || bag_of[i] >= B)) return;
     atomicAdd(&counts[inverse[i]], 1ull);
 }
 
@@ -1131,6 +1319,55 @@ __global__ void k_gather_host(const i64* __restrict__ keys, long n,
 
 // ============================================================== launchers
 
+// shared dispatch ladder of the plain and the bag-indirected reduce
+template <bool BAG>
+static void reduce_dispatch(const i64* inverse, const float* grads, long n,
+                            long dim, float* ugrads, u64* counts, long u,
+                            const int* bag_of, const i64* offsets, long B,
+                            int mode, hipStream_t stream) {
+    {
+        long ne = u * dim;
+        long mx = ne > u ? ne : u;
+        if (mx) k_reduce_reset<<<(int)((mx + 255) / 256), 256, 0, stream>>>(
+            ugrads, ne, counts, u);
+    }
+    if (n == 0) return;
+    int grid = cdiv(n, BLOCK);
+    // H must cover the block's worst-case distinct uids (BLOCK = 256):
+    // an undersized hash overflows most elements to DIRECT global atomics
+    // — measured 360 us/call at dim 65 with H=64 (75% overflow) vs the
+    // LDS-aggregated path's ~tens of us (profiles/bench_deepfm_dim64)
+    if (dim <= 16) {
+        // G=8: halves the serial per-group element chain vs G=16
+        // (nj = ceil(16/8) = 2 fragments)
+        const int H = 512;
+        size_t smem = H * 8 + (size_t)H * dim * 4;   // <= 40 KiB
+        k_reduce_lds<H, 8, 4, BAG><<<grid, BLOCK, smem, stream>>>(
+            inverse, grads, n, dim, ugrads, counts, bag_of, offsets, B,
+            mode);
+    } else if (dim <= 96) {
+        // G=16: quarter-length serial element chain vs G=64 (each group
+        // walks its G elements in order); GF=8 staging slots cover
+        // ceil(96/16)=6 fragments
+        const int H = 256;
+        size_t smem = H * 8 + (size_t)H * dim * 4;   // <= 98 KiB
+        k_reduce_lds<H, 16, 8, BAG><<<grid, BLOCK, smem, stream>>>(
+            inverse, grads, n, dim, ugrads, counts, bag_of, offsets, B,
+            mode);
+    } else if (dim <= 128) {
+        const int H = 128;
+        size_t smem = H * 8 + (size_t)H * dim * 4;   // <= 66 KiB
+        k_reduce_lds<H, 64, 4, BAG><<<grid, BLOCK, smem, stream>>>(
+            inverse, grads, n, dim, ugrads, counts, bag_of, offsets, B,
+            mode);
+    } else {
+        k_reduce_grads<BAG><<<grid1d(n * dim), BLOCK, 0, stream>>>(
+            inverse, grads, n, dim, ugrads, bag_of, offsets, B, mode);
+        k_reduce_counts<BAG><<<grid1d(n), BLOCK, 0, stream>>>(
+            inverse, n, counts, bag_of, B);
+    }
+}
+
 extern "C" {
 
 void emb_unique(const i64* keys, long n, u64* tk, int* tv, long cap,
@@ -1210,43 +1447,47 @@ void emb_gather_init(float* weights, float* state, long dim, long sd,
 void emb_reduce_by_inverse(const i64* inverse, const float* grads, long n,
                            long dim, float* ugrads, u64* counts, long u,
                            hipStream_t stream) {
-    {
-        long ne = u * dim;
-        long mx = ne > u ? ne : u;
-        if (mx) k_reduce_reset<<<(int)((mx + 255) / 256), 256, 0, stream>>>(
-            ugrads, ne, counts, u);
-    }
-    if (n == 0) return;
-    int grid = cdiv(n, BLOCK);
-    // H must cover the block's worst-case distinct uids (BLOCK = 256):
-    // an undersized hash overflows most elements to DIRECT global atomics
-    // — measured 360 us/call at dim 65 with H=64 (75% overflow) vs the
-    // LDS-aggregated path's ~tens of us (profiles/bench_deepfm_dim64)
-    if (dim <= 16) {
-        // G=8: halves the serial per-group element chain vs G=16
-        // (nj = ceil(16/8) = 2 fragments)
-        const int H = 512;
-        size_t smem = H * 8 + (size_t)H * dim * 4;   // <= 40 KiB
-        k_reduce_lds<H, 8><<<grid, BLOCK, smem, stream>>>(
-            inverse, grads, n, dim, ugrads, counts);
-    } else if (dim <= 96) {
-        // G=16: quarter-length serial element chain vs G=64 (each group
-        // walks its G elements in order); GF=8 staging slots cover
-        // ceil(96/16)=6 fragments
-        const int H = 256;
-        size_t smem = H * 8 + (size_t)H * dim * 4;   // <= 98 KiB
-        k_reduce_lds<H, 16, 8><<<grid, BLOCK, smem, stream>>>(
-            inverse, grads, n, dim, ugrads, counts);
-    } else if (dim <= 128) {
-        const int H = 128;
-        size_t smem = H * 8 + (size_t)H * dim * 4;   // <= 66 KiB
-        k_reduce_lds<H, 64><<<grid, BLOCK, smem, stream>>>(
-            inverse, grads, n, dim, ugrads, counts);
-    } else {
-        k_reduce_grads<<<grid1d(n * dim), BLOCK, 0, stream>>>(inverse, grads,
-                                                              n, dim, ugrads);
-        k_reduce_counts<<<grid1d(n), BLOCK, 0, stream>>>(inverse, n, counts);
-    }
+    reduce_dispatch<false>(inverse, grads, n, dim, ugrads, counts, u,
+                           nullptr, nullptr, 0, 0, stream);
+}
+
+// grads is the pooled [B, dim] gradient; n = number of elements (nnz)
+void emb_reduce_bags_by_inverse(const i64* inverse, const float* grad_out,
+                                long n, long dim, const int* bag_of,
+                                const i64* offsets, long B, int mode,
+                                float* ugrads, u64* counts, long u,
+                                hipStream_t stream) {
+    reduce_dispatch<true>(inverse, grad_out, n, dim, ugrads, counts, u,
+                          bag_of, offsets, B, mode, stream);
+}
+
+// map_kind: 0 = none, 1 = int64 (table slots), 2 = int32 (padded pos_of)
+void emb_pool_fwd(const float* rows, long R, long dim, const i64* inverse,
+                  long nnz, const void* map, int map_kind, long u,
+                  const i64* offsets, long B, int mode, float* out,
+                  int* bag_of, hipStream_t stream) {
+    if (B == 0 && (!bag_of || nnz == 0)) return;
+#define LAUNCH_POOL(G, CF, ILP)                                             \
+    do {                                                                    \
+        int gg = grid1d((B > 0 ? B : 1) * G);                               \
+        if (map_kind == 2)                                                  \
+            k_pool_fwd<G, CF, ILP, int><<<gg, BLOCK, 0, stream>>>(          \
+                rows, R, dim, inverse, nnz, (const int*)map, u, offsets, B, \
+                mode, out, bag_of);                                         \
+        else                                                                \
+            k_pool_fwd<G, CF, ILP, i64><<<gg, BLOCK, 0, stream>>>(          \
+                rows, R, dim, inverse, nnz,                                 \
+                map_kind ? (const i64*)map : nullptr, u, offsets, B, mode,  \
+                out, bag_of);                                               \
+    } while (0)
+    // G as in emb_gather_init (16 lanes up to dim 32, a full wave above);
+    // every rung keeps 16 row values in flight per lane
+    if (dim <= 16) LAUNCH_POOL(16, 1, 16);
+    else if (dim <= 32) LAUNCH_POOL(16, 2, 8);
+    else if (dim <= 64) LAUNCH_POOL(64, 1, 16);
+    else if (dim <= 128) LAUNCH_POOL(64, 2, 8);
+    else LAUNCH_POOL(64, 4, 4);   // dim > 256 loops over column passes
+#undef LAUNCH_POOL
 }
 
 #define LAUNCH_OPT(G, OPT)                                                  \

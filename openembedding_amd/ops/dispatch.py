@@ -55,6 +55,120 @@ def reduce_by_inverse(inverse: torch.Tensor, grads: torch.Tensor, u: int
     return ugrads, counts
 
 
+# ------------------------------------------------------------ multi-hot bags
+
+POOL_MODES = {"sum": 0, "mean": 1, "sqrtn": 2}
+
+
+def _bag_scale(offsets: torch.Tensor, nnz: int, mode: str,
+               dtype: torch.dtype) -> torch.Tensor:
+    """Combiner scale per bag: 1 (sum), 1/len (mean), 1/sqrt(len) (sqrtn);
+    0 for an empty bag. ``offsets`` is clamped to [0, nnz] like the
+    kernels do."""
+    off = offsets.clamp(0, nnz)
+    length = (off[1:] - off[:-1]).clamp(min=0).to(dtype)
+    if mode == "sum":
+        scale = torch.ones_like(length)
+    elif mode == "mean":
+        scale = 1.0 / length
+    else:
+        scale = 1.0 / length.sqrt()
+    return torch.where(length > 0, scale, torch.zeros_like(scale))
+
+
+def _bag_of(offsets: torch.Tensor, nnz: int) -> torch.Tensor:
+    """Bag of every element (int32 [nnz]); -1 at or beyond offsets[-1]."""
+    off = offsets.clamp(0, nnz)
+    pos = torch.arange(nnz, device=offsets.device)
+    bag = torch.bucketize(pos, off[1:].contiguous(), right=True)
+    bag = torch.where(bag < off.numel() - 1, bag, torch.full_like(bag, -1))
+    return bag.to(torch.int32)
+
+
+def pool_fwd(rows: torch.Tensor, inverse, row_map, offsets: torch.Tensor,
+             mode: str, want_bag_of: bool = True
+             ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Segment-pooled gather over ragged bags (the reference's ragged
+    sparse_read, exb.py:315-321, with the combiner fused in).
+
+    Bag b pools elements [offsets[b], offsets[b+1]). Element j reads
+    ``rows[row_map[inverse[j]]]``; ``inverse`` None is the identity,
+    ``row_map`` None reads ``rows[inverse[j]]``; a mapped row < 0 is a zero
+    row. rows [R, dim], inverse int64 [nnz], row_map int64/int32 [u],
+    offsets int64 [B+1] -> (out [B, dim], bag_of int32 [nnz]); bag_of is -1
+    for elements at or beyond offsets[-1] and feeds
+    ``reduce_bags_by_inverse``."""
+    if mode not in POOL_MODES:
+        raise ValueError(f"unknown pooling mode {mode!r}")
+    if _use_hip(rows) and rows.dtype == torch.float32:
+        ext = require_hip()   # f64 variables use the torch path below
+        if ext is not None:
+            return ext.pool_fwd(rows, inverse, row_map, offsets,
+                                POOL_MODES[mode], want_bag_of)
+    if inverse is not None:
+        nnz = inverse.numel()
+        idx = inverse
+    else:
+        nnz = row_map.numel() if row_map is not None else rows.shape[0]
+        idx = torch.arange(nnz, device=rows.device)
+    if row_map is not None:
+        idx = row_map.long().index_select(0, idx)
+    elems = rows.index_select(0, idx.clamp(min=0))
+    return pool_rows(elems, offsets, mode, live=idx >= 0)
+
+
+def pool_rows(elems: torch.Tensor, offsets: torch.Tensor, mode: str,
+              live: torch.Tensor = None
+              ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Pool already-gathered element rows [nnz, dim] per bag with plain
+    torch ops (differentiable w.r.t. ``elems``; sums in element order).
+    ``live`` [nnz] bool masks elements out. Returns (out [B, dim], bag_of)."""
+    nnz = elems.shape[0]
+    bag_of = _bag_of(offsets, nnz)
+    bag = bag_of.long()
+    keep = bag >= 0
+    if live is not None:
+        keep = keep & live
+    elems = torch.where(keep.unsqueeze(1), elems, torch.zeros_like(elems))
+    out = torch.zeros((offsets.numel() - 1, elems.shape[1]),
+                      dtype=elems.dtype, device=elems.device)
+    out = out.index_add(0, bag.clamp(min=0), elems)
+    out = out * _bag_scale(offsets, nnz, mode, elems.dtype).unsqueeze(1)
+    return out, bag_of
+
+
+def reduce_bags_by_inverse(inverse: torch.Tensor, grad_out: torch.Tensor,
+                           bag_of: torch.Tensor, offsets: torch.Tensor,
+                           mode: str, u: int
+                           ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Backward of ``pool_fwd``: the (ugrads [u, dim], counts int64 [u])
+    that ``reduce_by_inverse`` gives for the expanded gradient
+    ``grad_out[bag_of[e]] * scale[bag_of[e]]``. The HIP kernels never
+    build that [nnz, dim] expansion. Elements with bag_of < 0 add neither
+    gradient nor count; counts are value occurrences over all bags (the
+    reference's flat-value semantics)."""
+    if mode not in POOL_MODES:
+        raise ValueError(f"unknown pooling mode {mode!r}")
+    if _use_hip(grad_out) and grad_out.dtype == torch.float32:
+        ext = require_hip()
+        if ext is not None:
+            return ext.reduce_bags_by_inverse(inverse, grad_out, bag_of,
+                                              offsets, POOL_MODES[mode], u)
+    nnz = inverse.numel()
+    bag = bag_of.long()
+    live = bag >= 0
+    b = bag.clamp(min=0)
+    scale = _bag_scale(offsets, nnz, mode, grad_out.dtype)
+    g = grad_out.index_select(0, b) * scale.index_select(0, b).unsqueeze(1)
+    g = torch.where(live.unsqueeze(1), g, torch.zeros_like(g))
+    ugrads = torch.zeros((u, grad_out.shape[1]), dtype=grad_out.dtype,
+                         device=grad_out.device)
+    ugrads.index_add_(0, inverse, g)
+    counts = torch.zeros(u, dtype=torch.int64, device=grad_out.device)
+    counts.index_add_(0, inverse, live.to(torch.int64))
+    return ugrads, counts
+
+
 # ----------------------------------------------------------------- fused loss
 
 class _FusedBCEFn(torch.autograd.Function):

@@ -94,6 +94,8 @@ class PullHandle:
     padded: bool = False
     plan: Optional["_PaddedPlan"] = None
     owner_cpu: Optional[tuple] = None   # torch-fallback owner state
+    # pooled (multi-hot) pull: bag of every element, -1 for the tail
+    bag_of: Optional[torch.Tensor] = None
 
 
 class ShardedVariable:
@@ -201,6 +203,44 @@ class ShardedVariable:
         h = PullHandle(shape=indices.shape, unique=uk_buf, inverse=inverse,
                        bounded=True, u_dev=u_dev, slots=slots)
         return out.view(*indices.shape, self.shard.dim), h
+
+    def pull_pooled(self, values: torch.Tensor, offsets: torch.Tensor,
+                    mode: str, readonly: bool = False, pre=None):
+        """Pooled pull over ragged bags (the reference's RaggedTensor
+        sparse_read, exb.py:315-321, with the combiner fused in).
+
+        values: int [nnz_cap] flat ids; offsets: int64 [B+1] row splits;
+        mode: "sum" | "mean" | "sqrtn" -> (out [B, dim], handle). ``values``
+        may be longer than offsets[-1] (fixed capacity for graph capture);
+        the tail must hold the reserved key -1. ``pre`` is an (out, handle)
+        pair of an earlier flat ``pull(values)`` (prefetch).
+
+        Single GPU: fused — no [nnz, dim] tensor, zero host syncs. Every
+        other route pools its flat pull output. Collective like ``pull``."""
+        flat = values.reshape(-1).to(torch.int64)
+        dim = self.shard.dim
+        gpu = getattr(self.shard, "pull_bounded", None) is not None
+        remote = self.world_size > 1 or self._force_remote
+        if gpu and not remote and not readonly and pre is None:
+            self.stat_pull_indices += flat.numel()
+            ext = self.shard.ext
+            uk_buf, inverse, u_dev = ext.unique_bounded(flat, None)
+            out, slots, bag_of = self.shard.pull_pooled_bounded(
+                uk_buf, u_dev, inverse, offsets, ops.POOL_MODES[mode])
+            h = PullHandle(shape=flat.shape, unique=uk_buf, inverse=inverse,
+                           bounded=True, u_dev=u_dev, slots=slots,
+                           bag_of=bag_of)
+            return out, h
+        if pre is None:
+            if not gpu:
+                # the torch engine rejects the reserved key -1 loudly; a
+                # host read is free there, so drop the fixed-capacity tail
+                flat = flat[:max(0, int(offsets[-1]))]
+            pre = self.pull(flat, readonly=readonly)
+        rows, h = pre
+        out, h.bag_of = ops.pool_fwd(rows.reshape(-1, dim), None, None,
+                                     offsets, mode)
+        return out, h
 
     def _pull_remote_bounded(self, indices: torch.Tensor,
                              flat: torch.Tensor,
@@ -387,12 +427,13 @@ class ShardedVariable:
         h.owner_cpu = (valid, uk2, inv2)
         return rows_back
 
-    def _push_padded(self, h: PullHandle, g: torch.Tensor) -> None:
+    def _apply_padded(self, h: PullHandle, ugrads: torch.Tensor,
+                      counts: torch.Tensor) -> None:
+        """Route per-unique (ugrads, counts) over the padded wire and queue
+        them on the owner."""
         dim = self.shard.dim
         plan = h.plan
         world = self.world_size
-        nbuf = h.unique.numel()
-        ugrads, counts = ops.reduce_by_inverse(h.inverse, g, nbuf)
         if h.u_dev is not None:             # GPU engine
             ext = self.shard.ext
             send_p = ext.gather_pad(ugrads, counts, plan.send_src)
@@ -486,11 +527,29 @@ class ShardedVariable:
         """grads: [*shape, dim] gradient of the pulled weights."""
         dim = self.shard.dim
         g = grads.reshape(-1, dim)
+        ugrads, counts = ops.reduce_by_inverse(h.inverse, g,
+                                               h.unique.numel())
+        self._apply_reduced(h, ugrads, counts)
+
+    def push_pooled(self, h: PullHandle, grad_out: torch.Tensor,
+                    offsets: torch.Tensor, mode: str) -> None:
+        """grad_out: [B, dim] gradient of the pooled output of the matching
+        ``pull_pooled``. Same as ``push`` of the gradient expanded to
+        [nnz, dim], but the reduce reads ``grad_out`` through ``h.bag_of``
+        and that expansion is never built."""
+        g = grad_out.reshape(-1, self.shard.dim)
+        ugrads, counts = ops.reduce_bags_by_inverse(
+            h.inverse, g, h.bag_of, offsets, mode, h.unique.numel())
+        self._apply_reduced(h, ugrads, counts)
+
+    def _apply_reduced(self, h: PullHandle, ugrads: torch.Tensor,
+                       counts: torch.Tensor) -> None:
+        """Route per-unique (ugrads, counts) to their owners and queue them
+        for the commit (everything in push after the first reduce)."""
+        dim = self.shard.dim
         if h.padded:
-            self._push_padded(h, g)
+            self._apply_padded(h, ugrads, counts)
             return
-        u = h.unique.numel()
-        ugrads, counts = ops.reduce_by_inverse(h.inverse, g, u)
         if h.bounded:
             self.shard.push_slots(h.unique, h.u_dev, h.slots, ugrads, counts)
             return

@@ -33,7 +33,7 @@ from ..parallel import comm
 from ..parallel.sharded import ShardedVariable
 
 __all__ = [
-    "Embedding", "CombinedEmbedding", "Variable", "Context",
+    "Embedding", "EmbeddingBag", "CombinedEmbedding", "Variable", "Context",
     "distributed_optimizer", "DistributedOptimizer", "distributed_model",
     "Model", "save_server_model", "load_server_model",
     "save_as_original_model", "pulling", "sparse_read_as_dense",
@@ -291,6 +291,104 @@ class CombinedEmbedding(Embedding):
             return
         keys = field_ids.to(torch.int64) + self.field_offsets
         self.variable.prefetch(keys, match_ref=field_ids)
+
+
+class _PooledPullPushFn(torch.autograd.Function):
+    """forward = pooled sharded pull over ragged bags, backward = pooled
+    push: the [nnz, dim] rows and their gradient never reach autograd."""
+
+    @staticmethod
+    def forward(ctx, hook: torch.Tensor, values: torch.Tensor,
+                offsets: torch.Tensor, var: ShardedVariable, mode: str,
+                pre=None):
+        out, handle = var.pull_pooled(values, offsets, mode, pre=pre)
+        ctx.var = var
+        ctx.handle = handle
+        ctx.offsets = offsets
+        ctx.mode = mode
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        ctx.var.push_pooled(ctx.handle,
+                            grad_out.contiguous().to(ctx.var.shard.dtype),
+                            ctx.offsets, ctx.mode)
+        return (torch.zeros(0, device=grad_out.device), None, None, None,
+                None, None)
+
+
+class EmbeddingBag(Embedding):
+    """Multi-hot (ragged) embedding with a fused combiner — the reference's
+    RaggedTensor sparse_read (exb.py:315-321) plus the sum / mean / sqrtn
+    pooling CTR models apply to variable-length fields.
+
+    ``forward(values, offsets)``: ``values`` int [nnz_cap] flat ids,
+    ``offsets`` int64 [B+1] row splits (offsets[0] == 0, offsets[-1] <=
+    nnz_cap) -> [B, dim]; bag b pools values[offsets[b]:offsets[b+1]], an
+    empty bag is zeros. ``values`` may be longer than offsets[-1] — a fixed
+    capacity keeps the step hipGraph-capturable — and the tail must then
+    hold the reserved key -1.
+
+    ``validate=True`` checks ``offsets`` eagerly (device read; not allowed
+    under graph capture). Takes every ``Embedding`` keyword."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int,
+                 mode: str = "sum", validate: bool = False, **kw):
+        from ..ops.dispatch import POOL_MODES
+        if mode not in POOL_MODES:
+            raise ValueError(f"mode must be one of {sorted(POOL_MODES)}, "
+                             f"got {mode!r}")
+        super().__init__(num_embeddings, embedding_dim, **kw)
+        self.mode = mode
+        self.validate = validate
+
+    def _check_inputs(self, values: torch.Tensor,
+                      offsets: torch.Tensor) -> None:
+        if values.dim() != 1 or values.is_floating_point() \
+                or values.dtype == torch.bool:
+            raise TypeError("EmbeddingBag values must be a 1-D integer "
+                            f"tensor, got {values.dtype} "
+                            f"{tuple(values.shape)}")
+        if offsets.dim() != 1 or offsets.numel() < 1 \
+                or offsets.dtype != torch.int64:
+            raise TypeError("EmbeddingBag offsets must be a 1-D int64 "
+                            f"tensor of B+1 row splits, got {offsets.dtype} "
+                            f"{tuple(offsets.shape)}")
+        if values.device != offsets.device:
+            raise ValueError("EmbeddingBag values and offsets must be on "
+                             "the same device")
+        if not self.validate:
+            return
+        if values.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("EmbeddingBag(validate=True) reads offsets "
+                               "on the host and cannot run under graph "
+                               "capture")
+        off = offsets.tolist()
+        if off[0] != 0 or off[-1] > values.numel() \
+                or any(a > b for a, b in zip(off, off[1:])):
+            raise ValueError("EmbeddingBag offsets must start at 0, be "
+                             "non-decreasing and end at or below "
+                             f"len(values)={values.numel()}")
+
+    def forward(self, values: torch.Tensor,
+                offsets: torch.Tensor) -> torch.Tensor:
+        from ..ops.dispatch import pool_rows
+        self._check_inputs(values, offsets)
+        if self.sparse_as_dense:
+            # the fixed-capacity tail (-1) reads row 0 and is masked out
+            rows = self.dense(values.clamp(min=0))
+            return pool_rows(rows, offsets, self.mode)[0]
+        sharded = self.variable.sharded
+        if torch.is_grad_enabled() and self.grad_hook.requires_grad:
+            pre = self.variable._take_prefetched(values)
+            return _PooledPullPushFn.apply(self.grad_hook, values, offsets,
+                                           sharded, self.mode, pre)
+        out, _ = sharded.pull_pooled(values, offsets, self.mode,
+                                     readonly=True)
+        return out
+
+    def extra_repr(self):
+        return f"{super().extra_repr()}, pool={self.mode}"
 
 
 def _default_storage(ctx: Context) -> Storage:

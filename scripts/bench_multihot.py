@@ -1,0 +1,235 @@
+"""Fused multi-hot pooled step vs the same step composed from flat ops.
+
+    python scripts/bench_multihot.py [--out profiles/multihot_pool.md]
+
+fused    : EmbeddingBag forward (pooled pull) + backward (pooled push) +
+           commit — no [nnz, dim] tensor in either direction.
+composed : what a user wrote before EmbeddingBag existed — flat Embedding
+           pull of the values, torch segment pooling (bag ids from the
+           offsets, index_add, scale), autograd expansion back to
+           [nnz, dim], flat push, commit.
+
+Workload: batch 4096 bags, mean length 8 with a long tail (lengths drawn
+multinomially from log-normal weights, so every batch has the same nnz and
+both steps can also be timed as captured hipGraphs), 20% of the values on
+64 hot keys, array table of 2M rows, Adagrad, mode mean; dim 9 and 64.
+
+Method: both steps are warmed up, then timed in alternating blocks of
+``--block`` steps between device events over ``--blocks`` rounds (same
+process, same batches); reported is the per-step median and the p10-p90
+spread over blocks. Needs a GPU: there is no CPU fallback for a timing."""
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+B = 4096
+MEAN_LEN = 8
+VOCAB = 2_000_000
+N_BATCHES = 8
+
+
+def make_batches(device):
+    g = torch.Generator().manual_seed(0)
+    nnz = B * MEAN_LEN
+    out = []
+    for _ in range(N_BATCHES):
+        weights = torch.exp(1.2 * torch.randn(B, generator=g))
+        picks = torch.multinomial(weights, nnz, replacement=True, generator=g)
+        lens = torch.bincount(picks, minlength=B)
+        offsets = torch.cat([torch.zeros(1, dtype=torch.int64),
+                             lens.cumsum(0)])
+        vals = torch.randint(0, VOCAB, (nnz,), dtype=torch.int64, generator=g)
+        hot = torch.rand(nnz, generator=g) < 0.2
+        vals[hot] = torch.randint(0, 64, (int(hot.sum()),), generator=g)
+        out.append((vals.to(device), offsets.to(device), int(lens.max())))
+    return out
+
+
+def build(dim, device):
+    import openembedding_amd.torch as embed
+    from openembedding_amd.context import get_context
+    ctx = get_context(device)
+    bag = embed.EmbeddingBag(VOCAB, dim, mode="mean")
+    flat = embed.Embedding(VOCAB, dim)
+    for e in (bag, flat):
+        e.variable.set_optimizer("adagrad", learning_rate=0.01,
+                                 initial_accumulator_value=0.1,
+                                 epsilon=1e-10)
+    w = torch.randn(B, dim, device=device,
+                    generator=torch.Generator(device).manual_seed(1))
+    pos = torch.arange(B * MEAN_LEN, device=device)
+
+    def fused(vals, offsets):
+        out = bag(vals, offsets)
+        (out * w).sum().backward()
+        ctx.update_all_weights()
+        return out
+
+    def composed(vals, offsets):
+        rows = flat(vals)                                   # [nnz, dim]
+        bag_of = torch.bucketize(pos, offsets[1:], right=True)
+        lens = (offsets[1:] - offsets[:-1]).to(rows.dtype)
+        out = torch.zeros(B, dim, device=device).index_add(0, bag_of, rows)
+        out = out / lens.clamp(min=1).unsqueeze(1)
+        (out * w).sum().backward()
+        ctx.update_all_weights()
+        return out
+
+    return fused, composed, bag, flat
+
+
+def time_blocks(steps, batches, block, blocks):
+    """steps: {name: callable(i)} timed in alternating blocks."""
+    ms = {k: [] for k in steps}
+    i = 0
+    for _ in range(blocks):
+        for name, fn in steps.items():
+            start = torch.cuda.Event(enable_timing=True)
+            stop = torch.cuda.Event(enable_timing=True)
+            start.record()
+            for _ in range(block):
+                fn(i)
+                i += 1
+            stop.record()
+            stop.synchronize()
+            ms[name].append(start.elapsed_time(stop) / block)
+    return ms
+
+
+def summarize(ms):
+    out = {}
+    for k, v in ms.items():
+        q = statistics.quantiles(v, n=10)
+        out[k] = {"median_us": 1e3 * statistics.median(v),
+                  "p10_us": 1e3 * q[0], "p90_us": 1e3 * q[-1]}
+    return out
+
+
+def run_dim(dim, device, block, blocks, warmup):
+    import openembedding_amd.context as cm
+    import openembedding_amd.torch as api
+    if cm._context is not None:
+        cm._context.finalize()
+        cm._context = None
+    api._tracked.clear()
+    batches = make_batches(device)
+    fused, composed, bag, flat = build(dim, device)
+
+    # faster and different is not faster: at the timed size the fused
+    # forward must equal torch pooling of the same table's rows (the two
+    # variables draw different init rows, so each is checked on its own)
+    vals, offsets, _ = batches[0]
+    got = bag(vals, offsets).detach()
+    rows = bag.variable.sparse_read(vals)
+    bag_of = torch.bucketize(torch.arange(vals.numel(), device=device),
+                             offsets[1:], right=True)
+    lens = (offsets[1:] - offsets[:-1]).float().clamp(min=1).unsqueeze(1)
+    want = torch.zeros_like(got).index_add(0, bag_of, rows) / lens
+    torch.testing.assert_close(got, want, rtol=1e-5, atol=1e-6)
+
+    eager = {"fused": lambda i: fused(*batches[i % N_BATCHES][:2]),
+             "composed": lambda i: composed(*batches[i % N_BATCHES][:2])}
+    for i in range(warmup):
+        for fn in eager.values():
+            fn(i)
+    torch.cuda.synchronize()
+    res = {"eager": summarize(time_blocks(eager, batches, block, blocks))}
+
+    # captured: one graph per path over static input buffers
+    s_vals = batches[0][0].clone()
+    s_off = batches[0][1].clone()
+    graphs = {}
+    for name, fn in (("fused", fused), ("composed", composed)):
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                fn(s_vals, s_off)
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn(s_vals, s_off)
+        graphs[name] = g
+
+    def replay(name):
+        def run(i):
+            vals, offsets, _ = batches[i % N_BATCHES]
+            s_vals.copy_(vals)
+            s_off.copy_(offsets)
+            graphs[name].replay()
+        return run
+
+    captured = {k: replay(k) for k in graphs}
+    for i in range(warmup):
+        for fn in captured.values():
+            fn(i)
+    torch.cuda.synchronize()
+    res["graph"] = summarize(time_blocks(captured, batches, block, blocks))
+    res["max_bag_len"] = max(b[2] for b in batches)
+    for mode in ("eager", "graph"):
+        res[mode]["composed_over_fused"] = (
+            res[mode]["composed"]["median_us"]
+            / res[mode]["fused"]["median_us"])
+    return res
+
+
+def to_markdown(results, args):
+    lines = [
+        "# Multi-hot pooled step: fused vs composed (MI355X)",
+        "",
+        f"`scripts/bench_multihot.py`: batch {B} bags, nnz {B * MEAN_LEN} "
+        f"(mean length {MEAN_LEN}, long tail), array table of {VOCAB} rows, "
+        "Adagrad, mode mean. Per-step time from device events around "
+        f"alternating blocks of {args.block} steps, {args.blocks} blocks per "
+        f"path after {args.warmup} warm-up steps; median (p10-p90) in "
+        "microseconds. `eager` includes the host launch path, `graph` "
+        "replays one captured hipGraph per path (plus the two input "
+        "copies).",
+        "",
+        "| dim | mode | fused | composed | composed / fused |",
+        "|---|---|---|---|---|",
+    ]
+    for dim, r in results.items():
+        for mode in ("eager", "graph"):
+            f, c = r[mode]["fused"], r[mode]["composed"]
+            lines.append(
+                f"| {dim} | {mode} | {f['median_us']:.1f} "
+                f"({f['p10_us']:.1f}-{f['p90_us']:.1f}) | "
+                f"{c['median_us']:.1f} ({c['p10_us']:.1f}-"
+                f"{c['p90_us']:.1f}) | "
+                f"{r[mode]['composed_over_fused']:.2f}x |")
+    lines.append("")
+    lines.append("Longest bag over the batches: "
+                 f"{max(r['max_bag_len'] for r in results.values())}.")
+    return "\n".join(lines) + "\n"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dims", type=int, nargs="+", default=[9, 64])
+    ap.add_argument("--block", type=int, default=20)
+    ap.add_argument("--blocks", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--out", default=None, help="write a markdown table")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_multihot.py needs a GPU (no CPU fallback)")
+    from openembedding_amd.ops import require_hip
+    require_hip()
+    results = {d: run_dim(d, "cuda:0", args.block, args.blocks, args.warmup)
+               for d in args.dims}
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(to_markdown(results, args))
+    print(json.dumps({"bench": "multihot_pool", "results": results}))
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, os.path.dirname(os.path.dirname(
+        os.path.abspath(__file__))))
+    main()
