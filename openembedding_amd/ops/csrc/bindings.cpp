@@ -242,6 +242,10 @@ torch::Tensor gather_init(torch::Tensor weights, torch::Tensor state,
     } else {
         out = torch::empty({0}, weights.options());
     }
+    // uniform (init_cat 1): the kernel takes the span, subtracted in double
+    // and rounded once as core/rng.py does, so both sides multiply by the
+    // same float for any (minval, maxval)
+    if (init_cat == 1) p1 = p1 - p0;
     emb_gather_init(weights.data_ptr<float>(),
                     sd ? state.data_ptr<float>() : nullptr, dim, sd,
                     slots.data_ptr<i64>(),

@@ -127,13 +127,16 @@ DEV float normal01(u64 seed, u64 key, u64 col, u64 attempt) {
 
 DEV float init_value(int cat, float p0, float p1, float p2,
                      u64 seed, u64 key, u64 col) {
-    // constant: p0=value; uniform: p0=minval p1=maxval;
+    // constant: p0=value; uniform: p0=minval p1=maxval-minval;
     // normal: p0=mean p1=stddev p2=truncated (one-sided rejection, reference
     // EmbeddingInitializer.h:76-81 resamples only while (w-mean)/stddev > trunc)
     if (cat == INIT_CONSTANT) return p0;
     if (cat == INIT_UNIFORM) {
+        // the span arrives already rounded: the host subtracts in double
+        // and rounds once, like core/rng.py. 0.7f - 0.1f here would be one
+        // ulp off float(0.7 - 0.1) and break bit-identity with the oracle.
         float u = uniform01(seed, key, col, 0);
-        return p0 + u * (p1 - p0);
+        return p0 + u * p1;
     }
     float z = normal01(seed, key, col, 0);
     if (p2 > 0.1f) {
