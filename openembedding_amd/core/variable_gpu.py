@@ -219,16 +219,39 @@ class HipVariableShard(VariableShard):
 
     def pull_pooled_bounded(self, keys_buf: torch.Tensor,
                             u_dev: torch.Tensor, inverse: torch.Tensor,
-                            offsets: torch.Tensor, mode: int):
+                            offsets: torch.Tensor, mode: int,
+                            weights: torch.Tensor = None):
         """Sync-free pooled pull over ragged bags: lookup/insert, lazy init
         of new rows only (no output), then the pooling kernel reads
         ``self.weights`` straight through ``slots`` — no [nnz, dim] tensor
-        exists. Returns (out [B, dim], slots, bag_of [nnz])."""
+        exists. Returns (out [B, dim], slots, bag_of [nnz]); with
+        per-sample ``weights`` (float32 [nnz]) the weighted pool runs
+        instead and its bag_scale [B] is returned as a fourth value."""
         slots, new_mask = self._lookup_or_insert(keys_buf, u_dev)
         self._gather(keys_buf, slots, new_mask, False, u_dev=u_dev)
+        if weights is not None:
+            out, bag_of, bag_scale = self.ext.pool_fwd_weighted(
+                self.weights, inverse, slots, offsets, weights, mode)
+            return out, slots, bag_of, bag_scale
         out, bag_of = self.ext.pool_fwd(self.weights, inverse, slots,
                                         offsets, mode, True)
         return out, slots, bag_of
+
+    def pool_wgrad_slots(self, inverse: torch.Tensor, slots: torch.Tensor,
+                         weights: torch.Tensor, bag_of: torch.Tensor,
+                         bag_scale: torch.Tensor, out: torch.Tensor,
+                         grad_out: torch.Tensor, mode: int) -> torch.Tensor:
+        """Gradient of ``pull_pooled_bounded``'s weighted pool w.r.t. the
+        per-sample weights, dw [nnz], re-reading the table rows through the
+        ``slots`` saved by that pull instead of keeping them.
+
+        Contract: table rows change only at commit (``update_weights``), so
+        between a pull and the commit that follows it the rows behind
+        ``slots`` are the rows the forward pooled; call this before that
+        commit. Lazy init of later pulls touches new rows only, and a slab
+        regrow keeps every slot's content."""
+        return self.ext.pool_wgrad(self.weights, inverse, slots, weights,
+                                   bag_of, bag_scale, out, grad_out, mode)
 
     def push_slots(self, keys_buf, u_dev, slots, grads, counts) -> None:
         """Queue a bounded pre-reduced block whose table slots are already

@@ -44,6 +44,17 @@ void emb_reduce_bags_by_inverse(const i64*, const float*, long, long,
 void emb_pool_fwd(const float*, long, long, const i64*, long, const void*,
                   int, long, const i64*, long, int, float*, int*,
                   hipStream_t_);
+void emb_pool_fwd_weighted(const float*, long, long, const i64*, long,
+                           const void*, int, long, const i64*, long, int,
+                           const float*, float*, int*, float*, hipStream_t_);
+void emb_reduce_bags_weighted_by_inverse(const i64*, const float*, long, long,
+                                         const int*, const float*,
+                                         const float*, long, float*, u64*,
+                                         long, hipStream_t_);
+void emb_pool_wgrad(const float*, long, long, const i64*, long, const void*,
+                    int, long, const float*, const int*, const float*,
+                    const float*, const float*, long, int, float*,
+                    hipStream_t_);
 void emb_apply_optimizer(int, float*, float*, long, long, const i64*, long,
                          const float*, const u64*, const float*, const int*,
                          hipStream_t_);
@@ -368,6 +379,181 @@ std::tuple<torch::Tensor, torch::Tensor> reduce_bags_by_inverse(
                                (u64*)counts.data_ptr<i64>(), u,
                                cur_stream());
     return {ugrads, counts};
+}
+
+// ---- per-sample weights ------------------------------------------------
+
+// the (inverse -> map -> rows) index chain shared by the weighted pool and
+// its weight gradient; nnz is the element count it implies
+struct PoolChain {
+    const i64* inv_ptr = nullptr;
+    const void* map_ptr = nullptr;
+    int map_kind = 0;
+    long u = 0, nnz = 0;
+};
+
+static PoolChain pool_chain(const char* who, const torch::Tensor& rows,
+                            const OptTensor& inverse, const OptTensor& map) {
+    PoolChain c;
+    if (map.has_value()) {
+        CHECK_GPU(*map); CHECK_CONT(*map);
+        c.u = map->numel();
+        if (map->dtype() == torch::kInt64) {
+            c.map_kind = 1;
+            c.map_ptr = map->data_ptr<i64>();
+        } else {
+            TORCH_CHECK(map->dtype() == torch::kInt32, who,
+                        ": map must be int64 or int32");
+            c.map_kind = 2;
+            c.map_ptr = map->data_ptr<int>();
+        }
+    }
+    c.nnz = c.map_kind ? c.u : rows.size(0);
+    if (inverse.has_value()) {
+        CHECK_GPU(*inverse); CHECK_CONT(*inverse);
+        TORCH_CHECK(inverse->dtype() == torch::kInt64, who,
+                    ": inverse must be int64");
+        c.nnz = inverse->numel();
+        c.inv_ptr = inverse->data_ptr<i64>();
+    }
+    return c;
+}
+
+// pool_fwd with per-sample weights (float32 [nnz]): out[b] = scale_b *
+// sum_j w_j * row_j, scale_b = 1 | 1/sum w | 1/sqrt(sum w^2) (0 when the
+// denominator is 0). Returns (out [B, dim], bag_of int32 [nnz], bag_scale
+// float32 [B]); ``out_buf`` / ``scale_buf`` (optional) are written instead
+// of fresh allocations.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> pool_fwd_weighted(
+    torch::Tensor rows, OptTensor inverse, OptTensor map,
+    torch::Tensor offsets, torch::Tensor weights, int64_t mode,
+    OptTensor out_buf, OptTensor scale_buf) {
+    CHECK_GPU(rows); CHECK_CONT(rows);
+    CHECK_GPU(offsets); CHECK_CONT(offsets);
+    CHECK_GPU(weights); CHECK_CONT(weights);
+    TORCH_CHECK(rows.dtype() == torch::kFloat32 && rows.dim() == 2
+                && rows.size(1) >= 1,
+                "pool_fwd_weighted: rows must be float32 [R, dim >= 1]");
+    TORCH_CHECK(offsets.dtype() == torch::kInt64 && offsets.dim() == 1
+                && offsets.numel() >= 1,
+                "pool_fwd_weighted: offsets must be int64 [B+1]");
+    TORCH_CHECK(mode >= 0 && mode <= 2, "pool_fwd_weighted: bad mode");
+    PoolChain c = pool_chain("pool_fwd_weighted", rows, inverse, map);
+    TORCH_CHECK(weights.dtype() == torch::kFloat32 && weights.dim() == 1
+                && weights.numel() == c.nnz,
+                "pool_fwd_weighted: weights must be float32 [nnz]");
+    const c10::cuda::CUDAGuard guard(rows.device());
+    long R = rows.size(0), dim = rows.size(1);
+    long B = offsets.numel() - 1;
+    // caller-provided outputs (optional) must have exactly the shapes
+    // allocated here
+    auto out = out_buf.has_value() ? *out_buf
+                                   : torch::empty({B, dim}, rows.options());
+    auto bag_scale = scale_buf.has_value()
+        ? *scale_buf : torch::empty({B}, rows.options());
+    CHECK_GPU(out); CHECK_CONT(out);
+    CHECK_GPU(bag_scale); CHECK_CONT(bag_scale);
+    TORCH_CHECK(out.dtype() == torch::kFloat32 && out.dim() == 2
+                && out.size(0) == B && out.size(1) == dim,
+                "pool_fwd_weighted: out must be float32 [B, dim]");
+    TORCH_CHECK(bag_scale.dtype() == torch::kFloat32
+                && bag_scale.dim() == 1 && bag_scale.numel() == B,
+                "pool_fwd_weighted: bag_scale must be float32 [B]");
+    auto bag_of = torch::empty({c.nnz}, rows.options().dtype(torch::kInt32));
+    emb_pool_fwd_weighted(rows.data_ptr<float>(), R, dim, c.inv_ptr, c.nnz,
+                          c.map_ptr, c.map_kind, c.u,
+                          offsets.data_ptr<i64>(), B, (int)mode,
+                          weights.data_ptr<float>(), out.data_ptr<float>(),
+                          bag_of.data_ptr<int>(),
+                          bag_scale.data_ptr<float>(), cur_stream());
+    return {out, bag_of, bag_scale};
+}
+
+// reduce_bags_by_inverse with element e's factor weights[e] *
+// bag_scale[bag_of[e]] (bag_scale from pool_fwd_weighted); counts do not
+// depend on the weights.
+std::tuple<torch::Tensor, torch::Tensor> reduce_bags_weighted_by_inverse(
+    torch::Tensor inverse, torch::Tensor grad_out, torch::Tensor bag_of,
+    torch::Tensor weights, torch::Tensor bag_scale, int64_t u) {
+    CHECK_GPU(grad_out); CHECK_CONT(grad_out);
+    CHECK_GPU(inverse); CHECK_CONT(inverse);
+    CHECK_GPU(bag_of); CHECK_CONT(bag_of);
+    CHECK_GPU(weights); CHECK_CONT(weights);
+    CHECK_GPU(bag_scale); CHECK_CONT(bag_scale);
+    TORCH_CHECK(grad_out.dtype() == torch::kFloat32 && grad_out.dim() == 2,
+                "reduce_bags_weighted_by_inverse: grad_out must be float32 "
+                "[B, dim]");
+    TORCH_CHECK(inverse.dtype() == torch::kInt64
+                && bag_of.dtype() == torch::kInt32
+                && weights.dtype() == torch::kFloat32
+                && bag_scale.dtype() == torch::kFloat32,
+                "reduce_bags_weighted_by_inverse dtypes");
+    TORCH_CHECK(bag_of.numel() == inverse.numel()
+                && weights.numel() == inverse.numel(),
+                "reduce_bags_weighted_by_inverse: bag_of/weights/inverse "
+                "length mismatch");
+    TORCH_CHECK(bag_scale.numel() == grad_out.size(0),
+                "reduce_bags_weighted_by_inverse: bag_scale must be [B]");
+    TORCH_CHECK(u >= 0, "reduce_bags_weighted_by_inverse: bad u");
+    const c10::cuda::CUDAGuard guard(grad_out.device());
+    long n = inverse.numel();
+    long B = grad_out.size(0);
+    long dim = grad_out.size(1);
+    auto ugrads = torch::empty({u, dim}, grad_out.options());
+    auto counts = torch::empty({u}, grad_out.options().dtype(torch::kInt64));
+    emb_reduce_bags_weighted_by_inverse(
+        inverse.data_ptr<i64>(), grad_out.data_ptr<float>(), n, dim,
+        bag_of.data_ptr<int>(), weights.data_ptr<float>(),
+        bag_scale.data_ptr<float>(), B, ugrads.data_ptr<float>(),
+        (u64*)counts.data_ptr<i64>(), u, cur_stream());
+    return {ugrads, counts};
+}
+
+// dw [nnz]: gradient of pool_fwd_weighted w.r.t. its weights, reading
+// the rows through the same (inverse, map) chain; 0 for elements with
+// bag_of outside [0, B).
+torch::Tensor pool_wgrad(torch::Tensor rows, OptTensor inverse, OptTensor map,
+                         torch::Tensor weights, torch::Tensor bag_of,
+                         torch::Tensor bag_scale, torch::Tensor out,
+                         torch::Tensor grad_out, int64_t mode,
+                         OptTensor dw_buf) {
+    CHECK_GPU(rows); CHECK_CONT(rows);
+    CHECK_GPU(weights); CHECK_CONT(weights);
+    CHECK_GPU(bag_of); CHECK_CONT(bag_of);
+    CHECK_GPU(bag_scale); CHECK_CONT(bag_scale);
+    CHECK_GPU(out); CHECK_CONT(out);
+    CHECK_GPU(grad_out); CHECK_CONT(grad_out);
+    TORCH_CHECK(rows.dtype() == torch::kFloat32 && rows.dim() == 2,
+                "pool_wgrad: rows must be float32 [R, dim]");
+    TORCH_CHECK(out.dtype() == torch::kFloat32 && out.dim() == 2
+                && out.size(1) == rows.size(1)
+                && grad_out.dtype() == torch::kFloat32
+                && grad_out.sizes() == out.sizes(),
+                "pool_wgrad: out and grad_out must be float32 [B, dim]");
+    TORCH_CHECK(mode >= 0 && mode <= 2, "pool_wgrad: bad mode");
+    PoolChain c = pool_chain("pool_wgrad", rows, inverse, map);
+    TORCH_CHECK(weights.dtype() == torch::kFloat32
+                && weights.numel() == c.nnz,
+                "pool_wgrad: weights must be float32 [nnz]");
+    TORCH_CHECK(bag_of.dtype() == torch::kInt32 && bag_of.numel() == c.nnz,
+                "pool_wgrad: bag_of must be int32 [nnz]");
+    TORCH_CHECK(bag_scale.dtype() == torch::kFloat32
+                && bag_scale.numel() == out.size(0),
+                "pool_wgrad: bag_scale must be float32 [B]");
+    const c10::cuda::CUDAGuard guard(rows.device());
+    auto dw = dw_buf.has_value() ? *dw_buf
+                                 : torch::empty({c.nnz}, rows.options());
+    CHECK_GPU(dw); CHECK_CONT(dw);
+    TORCH_CHECK(dw.dtype() == torch::kFloat32 && dw.dim() == 1
+                && dw.numel() == c.nnz,
+                "pool_wgrad: dw must be float32 [nnz]");
+    emb_pool_wgrad(rows.data_ptr<float>(), rows.size(0), rows.size(1),
+                   c.inv_ptr, c.nnz, c.map_ptr, c.map_kind, c.u,
+                   weights.data_ptr<float>(), bag_of.data_ptr<int>(),
+                   bag_scale.data_ptr<float>(), out.data_ptr<float>(),
+                   grad_out.data_ptr<float>(), out.size(0), (int)mode,
+                   dw.data_ptr<float>(), cur_stream());
+    return dw;
 }
 
 void mask_tail(torch::Tensor keys, torch::Tensor grads, torch::Tensor counts,
@@ -935,6 +1121,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("reduce_bags_by_inverse", &reduce_bags_by_inverse,
           "grad reduce-by-key reading the pooled [B, dim] gradient through "
           "bag_of (no [nnz, dim] expansion)");
+    m.def("pool_fwd_weighted", &pool_fwd_weighted,
+          "pool_fwd with per-sample weights; also emits bag_of and the "
+          "per-bag combiner scale for the backward",
+          pybind11::arg("rows"), pybind11::arg("inverse"),
+          pybind11::arg("map"), pybind11::arg("offsets"),
+          pybind11::arg("weights"), pybind11::arg("mode"),
+          pybind11::arg("out") = pybind11::none(),
+          pybind11::arg("bag_scale") = pybind11::none());
+    m.def("reduce_bags_weighted_by_inverse",
+          &reduce_bags_weighted_by_inverse,
+          "bag-indirected grad reduce with the per-element factor "
+          "weights[e] * bag_scale[bag_of[e]]");
+    m.def("pool_wgrad", &pool_wgrad,
+          "gradient of the weighted pool w.r.t. its per-sample weights",
+          pybind11::arg("rows"), pybind11::arg("inverse"),
+          pybind11::arg("map"), pybind11::arg("weights"),
+          pybind11::arg("bag_of"), pybind11::arg("bag_scale"),
+          pybind11::arg("out"), pybind11::arg("grad_out"),
+          pybind11::arg("mode"), pybind11::arg("dw") = pybind11::none());
     m.def("apply_optimizer", &apply_optimizer, "fused sparse optimizer step");
     m.def("mask_tail", &mask_tail,
           "zero the garbage tail of a bounded block (enables multi-block "

@@ -517,6 +517,14 @@ DEV float pool_scale(int mode, long len) {
     return 1.0f;
 }
 
+// combiner scale of a weighted bag from its denominator (sum of w for mean,
+// sum of w^2 for sqrtn): TF's embedding_lookup_sparse with divide_no_nan
+DEV float pool_wscale(int mode, float den) {
+    if (mode == POOL_SUM) return 1.0f;
+    if (den == 0.0f) return 0.0f;
+    return mode == POOL_MEAN ? 1.0f / den : 1.0f / sqrtf(den);
+}
+
 // One G-lane group per bag, lanes over columns, PF_CF column fragments per
 // lane held in registers (dim <= PF_CF*G in one pass, wider rows loop).
 // The index chain (inverse -> map -> row) is resolved lane-parallel: lane l
@@ -535,6 +543,15 @@ DEV float pool_scale(int mode, long len) {
 // PF_CF * PF_ILP row values are in flight per lane; the launcher trades
 // column fragments for elements so narrow rows get the deeper element
 // preload (a 16-element chunk of a dim <= 16 bag is ONE load latency).
+//
+// WEIGHTED = true is the per-sample-weight variant: lane l loads the weight
+// of element j0+l beside its row index, the weight is broadcast with the
+// same __shfl as the row, the row is multiplied in before the add, and the
+// denominator (sum of w / sum of w^2) is accumulated in the same fixed
+// element order, so the result stays bitwise reproducible. Weights at or
+// beyond offsets[B] are never read. The bag's combiner scale goes to
+// ``bag_scale`` [B] for the backward. WEIGHTED = false compiles to the
+// plain kernel.
 
 // row of ``rows`` that element j reads, -1 = contributes zero (j outside
 // the bag, an index outside its table, or a mapped miss)
@@ -548,13 +565,16 @@ DEV long pool_row(long j, long e, const i64* __restrict__ inverse,
     return (row >= 0 && row < R) ? row : -1;
 }
 
-template <int G, int PF_CF, int PF_ILP, typename MapT>
+template <int G, int PF_CF, int PF_ILP, typename MapT,
+          bool WEIGHTED = false>
 __global__ void k_pool_fwd(const float* __restrict__ rows, long R, long dim,
                            const i64* __restrict__ inverse, long nnz,
                            const MapT* __restrict__ map, long u,
                            const i64* __restrict__ offsets, long B, int mode,
                            float* __restrict__ out,
-                           int* __restrict__ bag_of) {
+                           int* __restrict__ bag_of,
+                           const float* __restrict__ weights,
+                           float* __restrict__ bag_scale) {
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (bag_of) {
         const long nthreads = (long)gridDim.x * blockDim.x;
@@ -568,22 +588,34 @@ __global__ void k_pool_fwd(const float* __restrict__ rows, long R, long dim,
     const long s = pool_clamp(offsets[b], nnz);
     long e = pool_clamp(offsets[b + 1], nnz);
     if (e < s) e = s;
-    const float scale = pool_scale(mode, e - s);
+    float scale = 1.0f;
+    if constexpr (!WEIGHTED) scale = pool_scale(mode, e - s);
     const long nidx = map ? u : R;   // valid range of an inverse value
     for (long c0 = 0; c0 < dim; c0 += (long)G * PF_CF) {
         float acc[PF_CF];
         #pragma unroll
         for (int k = 0; k < PF_CF; ++k) acc[k] = 0.0f;
         long myrow = pool_row(s + lane, e, inverse, map, nidx, R);
+        // WEIGHTED only: this lane's element weight and the bag's
+        // denominator (every column pass recomputes the same value)
+        float myw = 0.0f, den = 0.0f;
+        if constexpr (WEIGHTED)
+            if (s + lane < e) myw = weights[s + lane];
         for (long j0 = s; j0 < e; j0 += G) {
             const long nextrow = pool_row(j0 + G + lane, e, inverse, map,
                                           nidx, R);
+            float nextw = 0.0f;
+            if constexpr (WEIGHTED)
+                if (j0 + G + lane < e) nextw = weights[j0 + G + lane];
             const int cnt = (int)((e - j0) < G ? (e - j0) : G);
             for (int t0 = 0; t0 < cnt; t0 += PF_ILP) {
                 long row[PF_ILP];
+                float wt[WEIGHTED ? PF_ILP : 1];
                 #pragma unroll
-                for (int t = 0; t < PF_ILP; ++t)    // t0 + t < G always
+                for (int t = 0; t < PF_ILP; ++t) {  // t0 + t < G always
                     row[t] = __shfl(myrow, t0 + t, G);
+                    if constexpr (WEIGHTED) wt[t] = __shfl(myw, t0 + t, G);
+                }
                 float v[PF_ILP][PF_CF];
                 #pragma unroll
                 for (int t = 0; t < PF_ILP; ++t) {
@@ -597,12 +629,25 @@ __global__ void k_pool_fwd(const float* __restrict__ rows, long R, long dim,
                 #pragma unroll
                 for (int t = 0; t < PF_ILP; ++t) {
                     if (t0 + t < cnt) {
-                        #pragma unroll
-                        for (int k = 0; k < PF_CF; ++k) acc[k] += v[t][k];
+                        if constexpr (WEIGHTED) {
+                            #pragma unroll
+                            for (int k = 0; k < PF_CF; ++k)
+                                acc[k] += wt[t] * v[t][k];
+                            den += (mode == POOL_SQRTN) ? wt[t] * wt[t]
+                                                        : wt[t];
+                        } else {
+                            #pragma unroll
+                            for (int k = 0; k < PF_CF; ++k) acc[k] += v[t][k];
+                        }
                     }
                 }
             }
             myrow = nextrow;
+            if constexpr (WEIGHTED) myw = nextw;
+        }
+        if constexpr (WEIGHTED) {
+            scale = pool_wscale(mode, den);
+            if (c0 == 0 && lane == 0) bag_scale[b] = scale;
         }
         #pragma unroll
         for (int k = 0; k < PF_CF; ++k) {
@@ -632,6 +677,12 @@ __global__ void k_pool_fwd(const float* __restrict__ rows, long R, long dim,
 // expansion autograd would build is never materialised. Elements whose
 // bag_of is outside [0, B) (the fixed-capacity tail) add neither gradient
 // nor count. BAG = false compiles to the plain kernel.
+//
+// WEIGHTED (with BAG) is the per-sample-weight backward: element e's factor
+// is w[e] * bag_scale[bag_of[e]] — the weight preloaded beside the bag, the
+// scale fetched from the forward's ``bag_scale`` with the staged gradient
+// fragment instead of recomputed from offsets. Counts do not depend on
+// weights. The non-weighted instantiations are unchanged.
 
 // row of the pooled gradient + scale for an element of bag ``bag``, or -1
 // to skip it
@@ -644,7 +695,15 @@ DEV long reduce_src(int bag, long n, const i64* __restrict__ offsets,
     return bag;
 }
 
-template <int H, int G, int GF = 4, bool BAG = false>
+// weighted form: the factor is w * bag_scale[bag]
+DEV long reduce_src_w(int bag, long B, float w,
+                      const float* __restrict__ bag_scale, float& scale) {
+    if (bag < 0 || bag >= B) return -1;
+    scale = w * bag_scale[bag];
+    return bag;
+}
+
+template <int H, int G, int GF = 4, bool BAG = false, bool WEIGHTED = false>
 __global__ void k_reduce_lds(const i64* __restrict__ inverse,
                              const float* __restrict__ grads,
                              long n, long dim,
@@ -652,7 +711,10 @@ __global__ void k_reduce_lds(const i64* __restrict__ inverse,
                              u64* __restrict__ counts,
                              const int* __restrict__ bag_of,
                              const i64* __restrict__ offsets,
-                             long B, int mode) {
+                             long B, int mode,
+                             const float* __restrict__ weights,
+                             const float* __restrict__ bag_scale) {
+    static_assert(BAG || !WEIGHTED, "WEIGHTED is a sub-variant of BAG");
     extern __shared__ char smem[];
     int* luid = (int*)smem;
     int* lcnt = (int*)(smem + H * 4);
@@ -683,6 +745,7 @@ __global__ void k_reduce_lds(const i64* __restrict__ inverse,
     // of the pooled gradient (-1 = skip the element) and the combiner
     // scale of the two staged elements
     int bags[BAG ? G : 1];
+    float wts[WEIGHTED ? G : 1];
     long gsrc[2] = {-1, -1};
     float gscale[2] = {1.0f, 1.0f};
     if constexpr (BAG) {
@@ -690,8 +753,12 @@ __global__ void k_reduce_lds(const i64* __restrict__ inverse,
         for (int t = 0; t < G; ++t) {
             long e = base + t;
             bags[t] = (e < n) ? bag_of[e] : -1;
+            if constexpr (WEIGHTED) wts[t] = (e < n) ? weights[e] : 0.0f;
         }
-        gsrc[0] = reduce_src(bags[0], n, offsets, B, mode, gscale[0]);
+        if constexpr (WEIGHTED)
+            gsrc[0] = reduce_src_w(bags[0], B, wts[0], bag_scale, gscale[0]);
+        else
+            gsrc[0] = reduce_src(bags[0], n, offsets, B, mode, gscale[0]);
         #pragma unroll
         for (int j = 0; j < GF; ++j)
             gfrag[0][j] = (j < nj && gsrc[0] >= 0 && lane + j * G < dim)
@@ -709,8 +776,12 @@ __global__ void k_reduce_lds(const i64* __restrict__ inverse,
         if constexpr (BAG) {
             if (t + 1 < G) {
                 const int nb = (t + 1) & 1;
-                gsrc[nb] = reduce_src(bags[t + 1], n, offsets, B, mode,
-                                      gscale[nb]);
+                if constexpr (WEIGHTED)
+                    gsrc[nb] = reduce_src_w(bags[t + 1], B, wts[t + 1],
+                                            bag_scale, gscale[nb]);
+                else
+                    gsrc[nb] = reduce_src(bags[t + 1], n, offsets, B, mode,
+                                          gscale[nb]);
                 #pragma unroll
                 for (int j = 0; j < GF; ++j)
                     gfrag[nb][j] = (j < nj && gsrc[nb] >= 0
@@ -757,20 +828,26 @@ __global__ void k_reduce_lds(const i64* __restrict__ inverse,
     }
 }
 
-template <bool BAG = false>
+template <bool BAG = false, bool WEIGHTED = false>
 __global__ void k_reduce_grads(const i64* __restrict__ inverse,
                                const float* __restrict__ grads,
                                long n, long dim,
                                float* __restrict__ ugrads,
                                const int* __restrict__ bag_of,
                                const i64* __restrict__ offsets,
-                               long B, int mode) {
+                               long B, int mode,
+                               const float* __restrict__ weights,
+                               const float* __restrict__ bag_scale) {
     long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n * dim) return;
     long i = e / dim, j = e % dim;
     if (BAG) {
         float scale = 1.0f;
-        long src = reduce_src(bag_of[i], n, offsets, B, mode, scale);
+        long src;
+        if constexpr (WEIGHTED)
+            src = reduce_src_w(bag_of[i], B, weights[i], bag_scale, scale);
+        else
+            src = reduce_src(bag_of[i], n, offsets, B, mode, scale);
         if (src < 0) return;
         atomicAdd(&ugrads[inverse[i] * dim + j],
                   grads[(u64)src * dim + j] * scale);
@@ -787,6 +864,75 @@ __global__ void k_reduce_counts(const i64* __restrict__ inverse, long n,
     if (i >= n) return;
     if (BAG && (bag_of[i] < 0 || bag_of[i] >= B)) return;
     atomicAdd(&counts[inverse[i]], 1ull);
+}
+
+// ------------------------------------------------- pooled weight gradient
+// dw[e] = scale_b * (<g_b, r_e> - c_e * <g_b, out_b>) for element e of bag
+// b = bag_of[e], with c_e = 0 (sum) | 1 (mean) | w_e * scale_b (sqrtn):
+// the gradient of the weighted pool w.r.t. its per-sample weights. r_e is
+// read from the table through inverse -> map exactly as pool_row does (a
+// miss is a zero row), so no [nnz, dim] tensor exists on the fused route.
+// One G-lane group per ELEMENT (not per bag: the longest bag does not set
+// the kernel's time), lanes over columns with WG_ILP independent column
+// fragments in flight; grad_out[b] and out[b] are shared by a bag's
+// elements and stay cache-hot. The cross-lane sum is a fixed-order
+// __shfl_xor tree and lane 0 stores with a plain store: deterministic, no
+// atomics. Elements whose bag_of is outside [0, B) (the tail) store 0;
+// their weights are never read.
+#define WG_ILP 4
+template <int G, typename MapT>
+__global__ void k_pool_wgrad(const float* __restrict__ rows, long R,
+                             long dim, const i64* __restrict__ inverse,
+                             long nnz, const MapT* __restrict__ map, long u,
+                             const float* __restrict__ weights,
+                             const int* __restrict__ bag_of,
+                             const float* __restrict__ bag_scale,
+                             const float* __restrict__ out,
+                             const float* __restrict__ grad_out, long B,
+                             int mode, float* __restrict__ dw) {
+    const long e = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    const int lane = threadIdx.x % G;
+    if (e >= nnz) return;               // whole group: G divides the block
+    const int bag = bag_of[e];
+    if (bag < 0 || bag >= B) {
+        if (lane == 0) dw[e] = 0.0f;
+        return;
+    }
+    const long nidx = map ? u : R;
+    const long row = pool_row(e, nnz, inverse, map, nidx, R);
+    const float scale = bag_scale[bag];
+    const float* __restrict__ g = grad_out + (u64)bag * dim;
+    const float* __restrict__ o = out + (u64)bag * dim;
+    const float* __restrict__ r = rows + (u64)(row >= 0 ? row : 0) * dim;
+    const bool need_o = mode != POOL_SUM;
+    float gr = 0.0f, go = 0.0f;
+    for (long c0 = lane; c0 < dim; c0 += (long)G * WG_ILP) {
+        float gv[WG_ILP], rv[WG_ILP], ov[WG_ILP];
+        #pragma unroll
+        for (int k = 0; k < WG_ILP; ++k) {
+            const long c = c0 + (long)k * G;
+            const bool in = c < dim;
+            gv[k] = in ? g[c] : 0.0f;
+            rv[k] = (in && row >= 0) ? r[c] : 0.0f;
+            ov[k] = (in && need_o) ? o[c] : 0.0f;
+        }
+        #pragma unroll
+        for (int k = 0; k < WG_ILP; ++k) {
+            gr += gv[k] * rv[k];
+            go += gv[k] * ov[k];
+        }
+    }
+    #pragma unroll
+    for (int m = G / 2; m > 0; m >>= 1) {
+        gr += __shfl_xor(gr, m, G);
+        go += __shfl_xor(go, m, G);
+    }
+    if (lane == 0) {
+        float cj = 0.0f;
+        if (mode == POOL_MEAN) cj = 1.0f;
+        else if (mode == POOL_SQRTN) cj = weights[e] * scale;
+        dw[e] = need_o ? scale * (gr - cj * go) : scale * gr;
+    }
 }
 
 // ------------------------------------------------------------- optimizers
@@ -1323,11 +1469,13 @@ __global__ void k_gather_host(const i64* __restrict__ keys, long n,
 // ============================================================== launchers
 
 // shared dispatch ladder of the plain and the bag-indirected reduce
-template <bool BAG>
+template <bool BAG, bool WEIGHTED = false>
 static void reduce_dispatch(const i64* inverse, const float* grads, long n,
                             long dim, float* ugrads, u64* counts, long u,
                             const int* bag_of, const i64* offsets, long B,
-                            int mode, hipStream_t stream) {
+                            int mode, hipStream_t stream,
+                            const float* weights = nullptr,
+                            const float* bag_scale = nullptr) {
     {
         long ne = u * dim;
         long mx = ne > u ? ne : u;
@@ -1345,30 +1493,64 @@ static void reduce_dispatch(const i64* inverse, const float* grads, long n,
         // (nj = ceil(16/8) = 2 fragments)
         const int H = 512;
         size_t smem = H * 8 + (size_t)H * dim * 4;   // <= 40 KiB
-        k_reduce_lds<H, 8, 4, BAG><<<grid, BLOCK, smem, stream>>>(
+        k_reduce_lds<H, 8, 4, BAG, WEIGHTED><<<grid, BLOCK, smem, stream>>>(
             inverse, grads, n, dim, ugrads, counts, bag_of, offsets, B,
-            mode);
+            mode, weights, bag_scale);
     } else if (dim <= 96) {
         // G=16: quarter-length serial element chain vs G=64 (each group
         // walks its G elements in order); GF=8 staging slots cover
         // ceil(96/16)=6 fragments
         const int H = 256;
         size_t smem = H * 8 + (size_t)H * dim * 4;   // <= 98 KiB
-        k_reduce_lds<H, 16, 8, BAG><<<grid, BLOCK, smem, stream>>>(
+        k_reduce_lds<H, 16, 8, BAG, WEIGHTED><<<grid, BLOCK, smem, stream>>>(
             inverse, grads, n, dim, ugrads, counts, bag_of, offsets, B,
-            mode);
+            mode, weights, bag_scale);
     } else if (dim <= 128) {
         const int H = 128;
         size_t smem = H * 8 + (size_t)H * dim * 4;   // <= 66 KiB
-        k_reduce_lds<H, 64, 4, BAG><<<grid, BLOCK, smem, stream>>>(
+        k_reduce_lds<H, 64, 4, BAG, WEIGHTED><<<grid, BLOCK, smem, stream>>>(
             inverse, grads, n, dim, ugrads, counts, bag_of, offsets, B,
-            mode);
+            mode, weights, bag_scale);
     } else {
-        k_reduce_grads<BAG><<<grid1d(n * dim), BLOCK, 0, stream>>>(
-            inverse, grads, n, dim, ugrads, bag_of, offsets, B, mode);
+        k_reduce_grads<BAG, WEIGHTED><<<grid1d(n * dim), BLOCK, 0, stream>>>(
+            inverse, grads, n, dim, ugrads, bag_of, offsets, B, mode,
+            weights, bag_scale);
         k_reduce_counts<BAG><<<grid1d(n), BLOCK, 0, stream>>>(
             inverse, n, counts, bag_of, B);
     }
+}
+
+// shared dispatch ladder of the plain and the weighted pooled gather;
+// map_kind: 0 = none, 1 = int64 (table slots), 2 = int32 (padded pos_of)
+template <bool WEIGHTED>
+static void pool_dispatch(const float* rows, long R, long dim,
+                          const i64* inverse, long nnz, const void* map,
+                          int map_kind, long u, const i64* offsets, long B,
+                          int mode, float* out, int* bag_of,
+                          const float* weights, float* bag_scale,
+                          hipStream_t stream) {
+    if (B == 0 && (!bag_of || nnz == 0)) return;
+#define LAUNCH_POOL(G, CF, ILP)                                             \
+    do {                                                                    \
+        int gg = grid1d((B > 0 ? B : 1) * G);                               \
+        if (map_kind == 2)                                                  \
+            k_pool_fwd<G, CF, ILP, int, WEIGHTED><<<gg, BLOCK, 0, stream>>>(\
+                rows, R, dim, inverse, nnz, (const int*)map, u, offsets, B, \
+                mode, out, bag_of, weights, bag_scale);                     \
+        else                                                                \
+            k_pool_fwd<G, CF, ILP, i64, WEIGHTED><<<gg, BLOCK, 0, stream>>>(\
+                rows, R, dim, inverse, nnz,                                 \
+                map_kind ? (const i64*)map : nullptr, u, offsets, B, mode,  \
+                out, bag_of, weights, bag_scale);                           \
+    } while (0)
+    // G as in emb_gather_init (16 lanes up to dim 32, a full wave above);
+    // every rung keeps 16 row values in flight per lane
+    if (dim <= 16) LAUNCH_POOL(16, 1, 16);
+    else if (dim <= 32) LAUNCH_POOL(16, 2, 8);
+    else if (dim <= 64) LAUNCH_POOL(64, 1, 16);
+    else if (dim <= 128) LAUNCH_POOL(64, 2, 8);
+    else LAUNCH_POOL(64, 4, 4);   // dim > 256 loops over column passes
+#undef LAUNCH_POOL
 }
 
 extern "C" {
@@ -1469,28 +1651,62 @@ void emb_pool_fwd(const float* rows, long R, long dim, const i64* inverse,
                   long nnz, const void* map, int map_kind, long u,
                   const i64* offsets, long B, int mode, float* out,
                   int* bag_of, hipStream_t stream) {
-    if (B == 0 && (!bag_of || nnz == 0)) return;
-#define LAUNCH_POOL(G, CF, ILP)                                             \
+    pool_dispatch<false>(rows, R, dim, inverse, nnz, map, map_kind, u,
+                         offsets, B, mode, out, bag_of, nullptr, nullptr,
+                         stream);
+}
+
+// weighted pool: also writes bag_scale [B]
+void emb_pool_fwd_weighted(const float* rows, long R, long dim,
+                           const i64* inverse, long nnz, const void* map,
+                           int map_kind, long u, const i64* offsets, long B,
+                           int mode, const float* weights, float* out,
+                           int* bag_of, float* bag_scale,
+                           hipStream_t stream) {
+    pool_dispatch<true>(rows, R, dim, inverse, nnz, map, map_kind, u,
+                        offsets, B, mode, out, bag_of, weights, bag_scale,
+                        stream);
+}
+
+// weighted pooled backward: element e's factor is
+// weights[e] * bag_scale[bag_of[e]]
+void emb_reduce_bags_weighted_by_inverse(const i64* inverse,
+                                         const float* grad_out, long n,
+                                         long dim, const int* bag_of,
+                                         const float* weights,
+                                         const float* bag_scale, long B,
+                                         float* ugrads, u64* counts, long u,
+                                         hipStream_t stream) {
+    reduce_dispatch<true, true>(inverse, grad_out, n, dim, ugrads, counts, u,
+                                bag_of, nullptr, B, 0, stream, weights,
+                                bag_scale);
+}
+
+// gradient of the weighted pool w.r.t. the per-sample weights, dw [nnz]
+void emb_pool_wgrad(const float* rows, long R, long dim, const i64* inverse,
+                    long nnz, const void* map, int map_kind, long u,
+                    const float* weights, const int* bag_of,
+                    const float* bag_scale, const float* out,
+                    const float* grad_out, long B, int mode, float* dw,
+                    hipStream_t stream) {
+    if (nnz == 0) return;
+#define LAUNCH_WGRAD(G)                                                     \
     do {                                                                    \
-        int gg = grid1d((B > 0 ? B : 1) * G);                               \
+        int gg = grid1d(nnz * G);                                           \
         if (map_kind == 2)                                                  \
-            k_pool_fwd<G, CF, ILP, int><<<gg, BLOCK, 0, stream>>>(          \
-                rows, R, dim, inverse, nnz, (const int*)map, u, offsets, B, \
-                mode, out, bag_of);                                         \
+            k_pool_wgrad<G, int><<<gg, BLOCK, 0, stream>>>(                 \
+                rows, R, dim, inverse, nnz, (const int*)map, u, weights,    \
+                bag_of, bag_scale, out, grad_out, B, mode, dw);             \
         else                                                                \
-            k_pool_fwd<G, CF, ILP, i64><<<gg, BLOCK, 0, stream>>>(          \
+            k_pool_wgrad<G, i64><<<gg, BLOCK, 0, stream>>>(                 \
                 rows, R, dim, inverse, nnz,                                 \
-                map_kind ? (const i64*)map : nullptr, u, offsets, B, mode,  \
-                out, bag_of);                                               \
+                map_kind ? (const i64*)map : nullptr, u, weights, bag_of,   \
+                bag_scale, out, grad_out, B, mode, dw);                     \
     } while (0)
-    // G as in emb_gather_init (16 lanes up to dim 32, a full wave above);
-    // every rung keeps 16 row values in flight per lane
-    if (dim <= 16) LAUNCH_POOL(16, 1, 16);
-    else if (dim <= 32) LAUNCH_POOL(16, 2, 8);
-    else if (dim <= 64) LAUNCH_POOL(64, 1, 16);
-    else if (dim <= 128) LAUNCH_POOL(64, 2, 8);
-    else LAUNCH_POOL(64, 4, 4);   // dim > 256 loops over column passes
-#undef LAUNCH_POOL
+    // G as on the gather ladder
+    if (dim <= 32) LAUNCH_WGRAD(16);
+    else LAUNCH_WGRAD(64);
+#undef LAUNCH_WGRAD
 }
 
 #define LAUNCH_OPT(G, OPT)                                                  \

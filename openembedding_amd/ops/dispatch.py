@@ -118,11 +118,13 @@ def pool_fwd(rows: torch.Tensor, inverse, row_map, offsets: torch.Tensor,
 
 
 def pool_rows(elems: torch.Tensor, offsets: torch.Tensor, mode: str,
-              live: torch.Tensor = None
+              live: torch.Tensor = None, weights: torch.Tensor = None
               ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Pool already-gathered element rows [nnz, dim] per bag with plain
     torch ops (differentiable w.r.t. ``elems``; sums in element order).
-    ``live`` [nnz] bool masks elements out. Returns (out [B, dim], bag_of)."""
+    ``live`` [nnz] bool masks elements out. ``weights`` [nnz] (optional)
+    are per-sample weights with the semantics of ``pool_fwd_weighted``,
+    differentiable too. Returns (out [B, dim], bag_of)."""
     nnz = elems.shape[0]
     bag_of = _bag_of(offsets, nnz)
     bag = bag_of.long()
@@ -130,10 +132,16 @@ def pool_rows(elems: torch.Tensor, offsets: torch.Tensor, mode: str,
     if live is not None:
         keep = keep & live
     elems = torch.where(keep.unsqueeze(1), elems, torch.zeros_like(elems))
+    if weights is not None:
+        w, scale = _weighted_scale(weights.to(elems.dtype), bag,
+                                   offsets.numel() - 1, mode)
+        elems = elems * w.unsqueeze(1)
+    else:
+        scale = _bag_scale(offsets, nnz, mode, elems.dtype)
     out = torch.zeros((offsets.numel() - 1, elems.shape[1]),
                       dtype=elems.dtype, device=elems.device)
     out = out.index_add(0, bag.clamp(min=0), elems)
-    out = out * _bag_scale(offsets, nnz, mode, elems.dtype).unsqueeze(1)
+    out = out * scale.unsqueeze(1)
     return out, bag_of
 
 
@@ -167,6 +175,133 @@ def reduce_bags_by_inverse(inverse: torch.Tensor, grad_out: torch.Tensor,
     counts = torch.zeros(u, dtype=torch.int64, device=grad_out.device)
     counts.index_add_(0, inverse, live.to(torch.int64))
     return ugrads, counts
+
+
+# ------------------------------------------------------- per-sample weights
+
+def _weighted_scale(weights: torch.Tensor, bag: torch.Tensor, B: int,
+                    mode: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(w [nnz] with the tail zeroed, scale [B]) of a weighted pool: scale
+    is 1 (sum), 1 / sum w (mean), 1 / sqrt(sum w^2) (sqrtn), and 0 where
+    that denominator is 0 (TF's divide_no_nan). The denominators run over
+    every position of the bag, a missed row included; weights of the tail
+    (bag < 0) are masked out before any use."""
+    w = torch.where(bag >= 0, weights, torch.zeros_like(weights))
+    if mode == "sum":
+        return w, torch.ones(B, dtype=w.dtype, device=w.device)
+    den = torch.zeros(B, dtype=w.dtype, device=w.device)
+    den = den.index_add(0, bag.clamp(min=0), w if mode == "mean" else w * w)
+    nz = den != 0
+    safe = torch.where(nz, den, torch.ones_like(den))
+    scale = 1.0 / safe if mode == "mean" else 1.0 / safe.sqrt()
+    return w, torch.where(nz, scale, torch.zeros_like(scale))
+
+
+def _gather_rows(rows: torch.Tensor, inverse, row_map, nnz: int
+                 ) -> torch.Tensor:
+    """[nnz, dim] rows element j reads through inverse -> row_map; a mapped
+    row < 0 is a zero row (torch path only)."""
+    idx = inverse if inverse is not None \
+        else torch.arange(nnz, device=rows.device)
+    if row_map is not None:
+        idx = row_map.long().index_select(0, idx)
+    elems = rows.index_select(0, idx.clamp(min=0))
+    return torch.where((idx >= 0).unsqueeze(1), elems,
+                       torch.zeros_like(elems))
+
+
+def pool_fwd_weighted(rows: torch.Tensor, inverse, row_map,
+                      offsets: torch.Tensor, weights: torch.Tensor, mode: str
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``pool_fwd`` with per-sample weights (TF's embedding_lookup_sparse
+    with ``sp_weights``): ``out[b] = scale_b * sum_j w_j * row_j`` with
+    scale_b = 1 (sum) | 1 / sum_j w_j (mean) | 1 / sqrt(sum_j w_j^2)
+    (sqrtn), 0 when that denominator is 0. weights float [nnz] (float32 on
+    the HIP path); weights at or beyond offsets[-1] are never used.
+    Returns (out [B, dim], bag_of int32 [nnz], bag_scale [B]); the last two
+    feed ``reduce_bags_weighted_by_inverse`` and ``pool_wgrad``."""
+    if mode not in POOL_MODES:
+        raise ValueError(f"unknown pooling mode {mode!r}")
+    if _use_hip(rows) and rows.dtype == torch.float32:
+        ext = require_hip()   # f64 variables use the torch path below
+        if ext is not None:
+            return ext.pool_fwd_weighted(rows, inverse, row_map, offsets,
+                                         weights, POOL_MODES[mode])
+    nnz = weights.numel()
+    B = offsets.numel() - 1
+    elems = _gather_rows(rows, inverse, row_map, nnz)
+    bag_of = _bag_of(offsets, nnz)
+    bag = bag_of.long()
+    w, scale = _weighted_scale(weights.to(rows.dtype), bag, B, mode)
+    out = torch.zeros((B, rows.shape[1]), dtype=rows.dtype,
+                      device=rows.device)
+    out.index_add_(0, bag.clamp(min=0), elems * w.unsqueeze(1))
+    return out * scale.unsqueeze(1), bag_of, scale
+
+
+def reduce_bags_weighted_by_inverse(inverse: torch.Tensor,
+                                    grad_out: torch.Tensor,
+                                    bag_of: torch.Tensor,
+                                    weights: torch.Tensor,
+                                    bag_scale: torch.Tensor, u: int
+                                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Backward of ``pool_fwd_weighted`` w.r.t. the rows: element e adds
+    ``grad_out[bag_of[e]] * (weights[e] * bag_scale[bag_of[e]])`` to its
+    key. Counts do not depend on the weights: a weight-0 element counts 1,
+    a tail element (bag_of < 0) 0."""
+    if _use_hip(grad_out) and grad_out.dtype == torch.float32:
+        ext = require_hip()
+        if ext is not None:
+            return ext.reduce_bags_weighted_by_inverse(
+                inverse, grad_out, bag_of, weights, bag_scale, u)
+    bag = bag_of.long()
+    live = bag >= 0
+    b = bag.clamp(min=0)
+    w = torch.where(live, weights.to(grad_out.dtype),
+                    torch.zeros((), dtype=grad_out.dtype,
+                                device=grad_out.device))
+    f = w * bag_scale.index_select(0, b)
+    g = grad_out.index_select(0, b) * f.unsqueeze(1)
+    g = torch.where(live.unsqueeze(1), g, torch.zeros_like(g))
+    ugrads = torch.zeros((u, grad_out.shape[1]), dtype=grad_out.dtype,
+                         device=grad_out.device)
+    ugrads.index_add_(0, inverse, g)
+    counts = torch.zeros(u, dtype=torch.int64, device=grad_out.device)
+    counts.index_add_(0, inverse, live.to(torch.int64))
+    return ugrads, counts
+
+
+def pool_wgrad(rows: torch.Tensor, inverse, row_map, weights: torch.Tensor,
+               bag_of: torch.Tensor, bag_scale: torch.Tensor,
+               out: torch.Tensor, grad_out: torch.Tensor, mode: str
+               ) -> torch.Tensor:
+    """Backward of ``pool_fwd_weighted`` w.r.t. the weights, dw [nnz]:
+    ``dw_j = scale_b * (<g_b, r_j> - c_j * <g_b, out_b>)`` with c_j = 0
+    (sum) | 1 (mean) | w_j * scale_b (sqrtn); r_j is the row element j read
+    (zero for a miss), g_b = grad_out[b]. 0 for tail elements. ``rows``,
+    ``inverse`` and ``row_map`` are those of the forward (both None: rows
+    are the gathered [nnz, dim] elements)."""
+    if mode not in POOL_MODES:
+        raise ValueError(f"unknown pooling mode {mode!r}")
+    if _use_hip(rows) and rows.dtype == torch.float32:
+        ext = require_hip()
+        if ext is not None:
+            return ext.pool_wgrad(rows, inverse, row_map, weights, bag_of,
+                                  bag_scale, out, grad_out, POOL_MODES[mode])
+    bag = bag_of.long()
+    live = bag >= 0
+    b = bag.clamp(min=0)
+    r = _gather_rows(rows, inverse, row_map, weights.numel())
+    g = grad_out.index_select(0, b)
+    s = bag_scale.index_select(0, b)
+    gr = (g * r).sum(1)
+    if mode == "sum":
+        dw = s * gr
+    else:
+        go = (g * out.index_select(0, b)).sum(1)
+        c = 1.0 if mode == "mean" else weights.to(rows.dtype) * s
+        dw = s * (gr - c * go)
+    return torch.where(live, dw, torch.zeros_like(dw))
 
 
 # ----------------------------------------------------------------- fused loss

@@ -96,6 +96,11 @@ class PullHandle:
     owner_cpu: Optional[tuple] = None   # torch-fallback owner state
     # pooled (multi-hot) pull: bag of every element, -1 for the tail
     bag_of: Optional[torch.Tensor] = None
+    # weighted pooled pull: combiner scale per bag, and — only off the
+    # fused route and only when the weights need a gradient — the flat
+    # [nnz, dim] rows the pool read
+    bag_scale: Optional[torch.Tensor] = None
+    pooled_rows: Optional[torch.Tensor] = None
 
 
 class ShardedVariable:
@@ -205,7 +210,8 @@ class ShardedVariable:
         return out.view(*indices.shape, self.shard.dim), h
 
     def pull_pooled(self, values: torch.Tensor, offsets: torch.Tensor,
-                    mode: str, readonly: bool = False, pre=None):
+                    mode: str, readonly: bool = False, pre=None,
+                    weights: torch.Tensor = None, wgrad: bool = False):
         """Pooled pull over ragged bags (the reference's RaggedTensor
         sparse_read, exb.py:315-321, with the combiner fused in).
 
@@ -214,6 +220,12 @@ class ShardedVariable:
         may be longer than offsets[-1] (fixed capacity for graph capture);
         the tail must hold the reserved key -1. ``pre`` is an (out, handle)
         pair of an earlier flat ``pull(values)`` (prefetch).
+
+        ``weights`` (optional): per-sample weights, float [nnz_cap] in the
+        variable's dtype, same device as ``values``; out[b] = scale_b *
+        sum_j w_j * row_j (``ops.pool_fwd_weighted``). Weights of the tail
+        are never used. ``wgrad`` says the matching ``push_pooled`` will be
+        asked for the weights' gradient.
 
         Single GPU: fused — no [nnz, dim] tensor, zero host syncs. Every
         other route pools its flat pull output. Collective like ``pull``."""
@@ -225,11 +237,18 @@ class ShardedVariable:
             self.stat_pull_indices += flat.numel()
             ext = self.shard.ext
             uk_buf, inverse, u_dev = ext.unique_bounded(flat, None)
-            out, slots, bag_of = self.shard.pull_pooled_bounded(
-                uk_buf, u_dev, inverse, offsets, ops.POOL_MODES[mode])
+            bag_scale = None
+            if weights is None:
+                out, slots, bag_of = self.shard.pull_pooled_bounded(
+                    uk_buf, u_dev, inverse, offsets, ops.POOL_MODES[mode])
+            else:
+                out, slots, bag_of, bag_scale = \
+                    self.shard.pull_pooled_bounded(
+                        uk_buf, u_dev, inverse, offsets,
+                        ops.POOL_MODES[mode], weights)
             h = PullHandle(shape=flat.shape, unique=uk_buf, inverse=inverse,
                            bounded=True, u_dev=u_dev, slots=slots,
-                           bag_of=bag_of)
+                           bag_of=bag_of, bag_scale=bag_scale)
             return out, h
         if pre is None:
             if not gpu:
@@ -238,8 +257,16 @@ class ShardedVariable:
                 flat = flat[:max(0, int(offsets[-1]))]
             pre = self.pull(flat, readonly=readonly)
         rows, h = pre
-        out, h.bag_of = ops.pool_fwd(rows.reshape(-1, dim), None, None,
-                                     offsets, mode)
+        rows = rows.reshape(-1, dim)
+        if weights is None:
+            out, h.bag_of = ops.pool_fwd(rows, None, None, offsets, mode)
+            return out, h
+        # the torch engine dropped the tail above: its weights go with it
+        out, h.bag_of, h.bag_scale = ops.pool_fwd_weighted(
+            rows, None, None, offsets,
+            weights[:rows.shape[0]].contiguous(), mode)
+        if wgrad:
+            h.pooled_rows = rows
         return out, h
 
     def _pull_remote_bounded(self, indices: torch.Tensor,
@@ -532,15 +559,44 @@ class ShardedVariable:
         self._apply_reduced(h, ugrads, counts)
 
     def push_pooled(self, h: PullHandle, grad_out: torch.Tensor,
-                    offsets: torch.Tensor, mode: str) -> None:
+                    offsets: torch.Tensor, mode: str,
+                    weights: torch.Tensor = None, out: torch.Tensor = None,
+                    wgrad: bool = False):
         """grad_out: [B, dim] gradient of the pooled output of the matching
         ``pull_pooled``. Same as ``push`` of the gradient expanded to
         [nnz, dim], but the reduce reads ``grad_out`` through ``h.bag_of``
-        and that expansion is never built."""
+        and that expansion is never built.
+
+        ``weights``: the per-sample weights given to the pull. With
+        ``wgrad`` (and ``out``, the pull's pooled output) the gradient
+        w.r.t. the weights, dw [nnz_cap], is returned: on the fused route it
+        re-reads the table through the handle's slots, which is valid
+        because rows change only at commit — so call this before
+        ``update_weights``; the other routes kept their flat rows."""
         g = grad_out.reshape(-1, self.shard.dim)
-        ugrads, counts = ops.reduce_bags_by_inverse(
-            h.inverse, g, h.bag_of, offsets, mode, h.unique.numel())
+        if weights is None:
+            ugrads, counts = ops.reduce_bags_by_inverse(
+                h.inverse, g, h.bag_of, offsets, mode, h.unique.numel())
+            self._apply_reduced(h, ugrads, counts)
+            return None
+        nnz = h.bag_of.numel()
+        w = weights[:nnz].contiguous()
+        ugrads, counts = ops.reduce_bags_weighted_by_inverse(
+            h.inverse, g, h.bag_of, w, h.bag_scale, h.unique.numel())
+        dw = None
+        if wgrad:
+            if h.pooled_rows is not None:
+                dw = ops.pool_wgrad(h.pooled_rows, None, None, w, h.bag_of,
+                                    h.bag_scale, out, g, mode)
+                h.pooled_rows = None
+            else:
+                dw = self.shard.pool_wgrad_slots(
+                    h.inverse, h.slots, w, h.bag_of, h.bag_scale, out, g,
+                    ops.POOL_MODES[mode])
+            if nnz < weights.numel():   # tail the torch engine dropped
+                dw = torch.cat([dw, dw.new_zeros(weights.numel() - nnz)])
         self._apply_reduced(h, ugrads, counts)
+        return dw
 
     def _apply_reduced(self, h: PullHandle, ugrads: torch.Tensor,
                        counts: torch.Tensor) -> None:

@@ -317,6 +317,40 @@ class _PooledPullPushFn(torch.autograd.Function):
                 None, None)
 
 
+class _WeightedPooledPullPushFn(torch.autograd.Function):
+    """``_PooledPullPushFn`` with per-sample weights: the backward also
+    returns dw for the weights when they require a gradient (learned
+    attention weights); data weights cost no extra launch."""
+
+    @staticmethod
+    def forward(ctx, hook: torch.Tensor, values: torch.Tensor,
+                offsets: torch.Tensor, weights: torch.Tensor,
+                var: ShardedVariable, mode: str, pre=None):
+        wgrad = ctx.needs_input_grad[3]
+        w = weights.detach().to(var.shard.dtype).contiguous()
+        out, handle = var.pull_pooled(values, offsets, mode, pre=pre,
+                                      weights=w, wgrad=wgrad)
+        ctx.var = var
+        ctx.handle = handle
+        ctx.offsets = offsets
+        ctx.mode = mode
+        ctx.wgrad = wgrad
+        ctx.wdtype = weights.dtype
+        ctx.save_for_backward(w, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        w, out = ctx.saved_tensors
+        dw = ctx.var.push_pooled(
+            ctx.handle, grad_out.contiguous().to(ctx.var.shard.dtype),
+            ctx.offsets, ctx.mode, weights=w, out=out, wgrad=ctx.wgrad)
+        if dw is not None:
+            dw = dw.to(ctx.wdtype)
+        return (torch.zeros(0, device=grad_out.device), None, None, dw,
+                None, None, None)
+
+
 class EmbeddingBag(Embedding):
     """Multi-hot (ragged) embedding with a fused combiner — the reference's
     RaggedTensor sparse_read (exb.py:315-321) plus the sum / mean / sqrtn
@@ -329,8 +363,17 @@ class EmbeddingBag(Embedding):
     capacity keeps the step hipGraph-capturable — and the tail must then
     hold the reserved key -1.
 
-    ``validate=True`` checks ``offsets`` eagerly (device read; not allowed
-    under graph capture). Takes every ``Embedding`` keyword."""
+    ``forward(values, offsets, per_sample_weights=w)``: ``w`` float
+    [nnz_cap] weights every element (TF's ``embedding_lookup_sparse`` with
+    ``sp_weights``): ``out[b] = scale_b * sum_j w_j * row(values[j])`` with
+    scale_b = 1 (sum), 1 / sum_j w_j (mean), 1 / sqrt(sum_j w_j^2) (sqrtn)
+    and 0 where that denominator is 0. Negative weights are legal, weights
+    of the tail are never used, and ``w`` receives a gradient when it
+    requires one (attention pooling with learned weights).
+
+    ``validate=True`` checks ``offsets`` (and that the live weights are
+    finite) eagerly (device read; not allowed under graph capture). Takes
+    every ``Embedding`` keyword."""
 
     def __init__(self, num_embeddings: int, embedding_dim: int,
                  mode: str = "sum", validate: bool = False, **kw):
@@ -342,8 +385,8 @@ class EmbeddingBag(Embedding):
         self.mode = mode
         self.validate = validate
 
-    def _check_inputs(self, values: torch.Tensor,
-                      offsets: torch.Tensor) -> None:
+    def _check_inputs(self, values: torch.Tensor, offsets: torch.Tensor,
+                      weights: torch.Tensor = None) -> None:
         if values.dim() != 1 or values.is_floating_point() \
                 or values.dtype == torch.bool:
             raise TypeError("EmbeddingBag values must be a 1-D integer "
@@ -357,6 +400,18 @@ class EmbeddingBag(Embedding):
         if values.device != offsets.device:
             raise ValueError("EmbeddingBag values and offsets must be on "
                              "the same device")
+        if weights is not None:
+            if weights.dim() != 1 or not weights.is_floating_point():
+                raise TypeError("EmbeddingBag per_sample_weights must be a "
+                                f"1-D floating-point tensor, got "
+                                f"{weights.dtype} {tuple(weights.shape)}")
+            if weights.numel() != values.numel():
+                raise ValueError("EmbeddingBag per_sample_weights must have "
+                                 f"len(values)={values.numel()} elements, "
+                                 f"got {weights.numel()}")
+            if weights.device != values.device:
+                raise ValueError("EmbeddingBag per_sample_weights and "
+                                 "values must be on the same device")
         if not self.validate:
             return
         if values.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -369,10 +424,17 @@ class EmbeddingBag(Embedding):
             raise ValueError("EmbeddingBag offsets must start at 0, be "
                              "non-decreasing and end at or below "
                              f"len(values)={values.numel()}")
+        if weights is not None \
+                and not bool(torch.isfinite(weights[:off[-1]]).all()):
+            raise ValueError("EmbeddingBag per_sample_weights must be "
+                             "finite inside the bags")
 
-    def forward(self, values: torch.Tensor,
-                offsets: torch.Tensor) -> torch.Tensor:
+    def forward(self, values: torch.Tensor, offsets: torch.Tensor,
+                per_sample_weights: torch.Tensor = None) -> torch.Tensor:
         from ..ops.dispatch import pool_rows
+        if per_sample_weights is not None:
+            return self._forward_weighted(values, offsets,
+                                          per_sample_weights)
         self._check_inputs(values, offsets)
         if self.sparse_as_dense:
             # the fixed-capacity tail (-1) reads row 0 and is masked out
@@ -385,6 +447,34 @@ class EmbeddingBag(Embedding):
                                            sharded, self.mode, pre)
         out, _ = sharded.pull_pooled(values, offsets, self.mode,
                                      readonly=True)
+        return out
+
+    def _forward_weighted(self, values: torch.Tensor, offsets: torch.Tensor,
+                          weights: torch.Tensor) -> torch.Tensor:
+        from ..ops.dispatch import pool_rows
+        self._check_inputs(values, offsets, weights)
+        if self.sparse_as_dense:
+            rows = self.dense(values.clamp(min=0))
+            return pool_rows(rows, offsets, self.mode, weights=weights)[0]
+        sharded = self.variable.sharded
+        if torch.is_grad_enabled() and self.grad_hook.requires_grad:
+            pre = self.variable._take_prefetched(values)
+            return _WeightedPooledPullPushFn.apply(
+                self.grad_hook, values, offsets, weights, sharded, self.mode,
+                pre)
+        if torch.is_grad_enabled() and weights.requires_grad:
+            # frozen table, learned weights: pool the read-only rows with
+            # torch ops so that autograd still reaches the weights (the
+            # torch engine rejects the tail key -1; a host read is free
+            # there, so drop the tail)
+            n = values.numel() if values.is_cuda \
+                else max(0, int(offsets[-1]))
+            rows = self.variable.sparse_read(values[:n])
+            return pool_rows(rows, offsets, self.mode,
+                             weights=weights[:n])[0]
+        w = weights.detach().to(sharded.shard.dtype).contiguous()
+        out, _ = sharded.pull_pooled(values, offsets, self.mode,
+                                     readonly=True, weights=w)
         return out
 
     def extra_repr(self):

@@ -1,6 +1,8 @@
 """Fused multi-hot pooled step vs the same step composed from flat ops.
 
     python scripts/bench_multihot.py [--out profiles/multihot_pool.md]
+    python scripts/bench_multihot.py --weighted \
+        [--out profiles/multihot_pool_weighted.md]
 
 fused    : EmbeddingBag forward (pooled pull) + backward (pooled push) +
            commit — no [nnz, dim] tensor in either direction.
@@ -8,6 +10,14 @@ composed : what a user wrote before EmbeddingBag existed — flat Embedding
            pull of the values, torch segment pooling (bag ids from the
            offsets, index_add, scale), autograd expansion back to
            [nnz, dim], flat push, commit.
+
+``--weighted`` times the per-sample-weight step instead: fused is
+EmbeddingBag(values, offsets, per_sample_weights=w), composed multiplies the
+flat rows by w before the same torch pooling (weighted mean: divided by the
+bag's sum of w). Both are timed with data weights (no gradient) and with
+weights that require a gradient (``_wg``: the fused step adds k_pool_wgrad,
+the composed step autograd's [nnz, dim] product backward), and the unweighted
+fused step runs in the same alternating blocks for reference.
 
 Workload: batch 4096 bags, mean length 8 with a long tail (lengths drawn
 multinomially from log-normal weights, so every batch has the same nnz and
@@ -81,6 +91,169 @@ def build(dim, device):
         return out
 
     return fused, composed, bag, flat
+
+
+def build_weighted(dim, device):
+    """{name: step(vals, offsets, w)}; w is [nnz] in [0.25, 2], a leaf that
+    requires grad for the ``_wg`` steps."""
+    import openembedding_amd.torch as embed
+    from openembedding_amd.context import get_context
+    ctx = get_context(device)
+    bag = embed.EmbeddingBag(VOCAB, dim, mode="mean")
+    flat = embed.Embedding(VOCAB, dim)
+    for e in (bag, flat):
+        e.variable.set_optimizer("adagrad", learning_rate=0.01,
+                                 initial_accumulator_value=0.1,
+                                 epsilon=1e-10)
+    t = torch.randn(B, dim, device=device,
+                    generator=torch.Generator(device).manual_seed(1))
+    pos = torch.arange(B * MEAN_LEN, device=device)
+
+    def finish(out, w):
+        if w is not None:
+            w.grad = None
+        (out * t).sum().backward()
+        ctx.update_all_weights()
+        return out
+
+    def fused(vals, offsets, w):
+        return finish(bag(vals, offsets, per_sample_weights=w), w)
+
+    def unweighted(vals, offsets, w):
+        return finish(bag(vals, offsets), None)
+
+    def composed(vals, offsets, w):
+        rows = flat(vals) * w.unsqueeze(1)                  # [nnz, dim]
+        bag_of = torch.bucketize(pos, offsets[1:], right=True)
+        out = torch.zeros(B, dim, device=device).index_add(0, bag_of, rows)
+        den = torch.zeros(B, device=device).index_add(0, bag_of, w)
+        out = out / torch.where(den != 0, den,
+                                torch.ones_like(den)).unsqueeze(1)
+        return finish(out, w)
+
+    return {"fused": fused, "composed": composed,
+            "unweighted_fused": unweighted}, bag
+
+
+def run_dim_weighted(dim, device, block, blocks, warmup):
+    import openembedding_amd.context as cm
+    import openembedding_amd.torch as api
+    if cm._context is not None:
+        cm._context.finalize()
+        cm._context = None
+    api._tracked.clear()
+    batches = make_batches(device)
+    g = torch.Generator().manual_seed(2)
+    ws = [(torch.rand(B * MEAN_LEN, generator=g) * 1.75 + 0.25).to(device)
+          for _ in batches]
+    fns, bag = build_weighted(dim, device)
+
+    # the fused weighted forward must equal torch pooling of the same rows
+    vals, offsets, _ = batches[0]
+    got = bag(vals, offsets, per_sample_weights=ws[0]).detach()
+    rows = bag.variable.sparse_read(vals) * ws[0].unsqueeze(1)
+    bag_of = torch.bucketize(torch.arange(vals.numel(), device=device),
+                             offsets[1:], right=True)
+    den = torch.zeros(B, device=device).index_add(0, bag_of, ws[0])
+    want = torch.zeros_like(got).index_add(0, bag_of, rows) \
+        / torch.where(den != 0, den, torch.ones_like(den)).unsqueeze(1)
+    torch.testing.assert_close(got, want, rtol=1e-5, atol=1e-6)
+
+    # (step name, function, weights require grad)
+    plan = [("fused", "fused", False), ("composed", "composed", False),
+            ("fused_wg", "fused", True), ("composed_wg", "composed", True),
+            ("unweighted_fused", "unweighted_fused", False)]
+    wg = [w.clone().requires_grad_() for w in ws]
+
+    def eager_step(fn, grad):
+        def run(i):
+            vals, offsets, _ = batches[i % N_BATCHES]
+            fn(vals, offsets, (wg if grad else ws)[i % N_BATCHES])
+        return run
+
+    eager = {name: eager_step(fns[f], grad) for name, f, grad in plan}
+    for i in range(warmup):
+        for fn in eager.values():
+            fn(i)
+    torch.cuda.synchronize()
+    res = {"eager": summarize(time_blocks(eager, batches, block, blocks))}
+
+    s_vals = batches[0][0].clone()
+    s_off = batches[0][1].clone()
+    s_w = {False: ws[0].clone(), True: ws[0].clone().requires_grad_()}
+    graphs = {}
+    for name, f, grad in plan:
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                fns[f](s_vals, s_off, s_w[grad])
+        torch.cuda.current_stream().wait_stream(side)
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            fns[f](s_vals, s_off, s_w[grad])
+        graphs[name] = (gr, grad)
+
+    def replay(name):
+        gr, grad = graphs[name]
+
+        def run(i):
+            vals, offsets, _ = batches[i % N_BATCHES]
+            s_vals.copy_(vals)
+            s_off.copy_(offsets)
+            with torch.no_grad():
+                s_w[grad].copy_(ws[i % N_BATCHES])
+            gr.replay()
+        return run
+
+    captured = {k: replay(k) for k in graphs}
+    for i in range(warmup):
+        for fn in captured.values():
+            fn(i)
+    torch.cuda.synchronize()
+    res["graph"] = summarize(time_blocks(captured, batches, block, blocks))
+    res["max_bag_len"] = max(b[2] for b in batches)
+    for mode in ("eager", "graph"):
+        for suf in ("", "_wg"):
+            res[mode]["composed_over_fused" + suf] = (
+                res[mode]["composed" + suf]["median_us"]
+                / res[mode]["fused" + suf]["median_us"])
+    return res
+
+
+def to_markdown_weighted(results, args):
+    cell = lambda r: (f"{r['median_us']:.1f} ({r['p10_us']:.1f}-"
+                      f"{r['p90_us']:.1f})")
+    lines = [
+        "# Weighted multi-hot pooled step: fused vs composed (MI355X)",
+        "",
+        f"`scripts/bench_multihot.py --weighted`: batch {B} bags, nnz "
+        f"{B * MEAN_LEN} (mean length {MEAN_LEN}, long tail), array table "
+        f"of {VOCAB} rows, Adagrad, mode mean, weights uniform in "
+        "[0.25, 2]. Per-step time from device events around alternating "
+        f"blocks of {args.block} steps, {args.blocks} blocks per path after "
+        f"{args.warmup} warm-up steps, all paths in one process on the same "
+        "batches; median (p10-p90) in microseconds. `w` = data weights (no "
+        "gradient), `w+dw` = weights that require a gradient; `unweighted` "
+        "is the unweighted fused step in the same alternating blocks.",
+        "",
+        "| dim | mode | weights | fused | composed | composed / fused | "
+        "unweighted fused |",
+        "|---|---|---|---|---|---|---|",
+    ]
+    for dim, r in results.items():
+        for mode in ("eager", "graph"):
+            for suf, label in (("", "w"), ("_wg", "w+dw")):
+                lines.append(
+                    f"| {dim} | {mode} | {label} | "
+                    f"{cell(r[mode]['fused' + suf])} | "
+                    f"{cell(r[mode]['composed' + suf])} | "
+                    f"{r[mode]['composed_over_fused' + suf]:.2f}x | "
+                    f"{cell(r[mode]['unweighted_fused'])} |")
+    lines.append("")
+    lines.append("Longest bag over the batches: "
+                 f"{max(r['max_bag_len'] for r in results.values())}.")
+    return "\n".join(lines) + "\n"
 
 
 def time_blocks(steps, batches, block, blocks):
@@ -216,17 +389,23 @@ def main():
     ap.add_argument("--blocks", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--out", default=None, help="write a markdown table")
+    ap.add_argument("--weighted", action="store_true",
+                    help="time the per-sample-weight step (with and "
+                         "without a gradient for the weights)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_multihot.py needs a GPU (no CPU fallback)")
     from openembedding_amd.ops import require_hip
     require_hip()
-    results = {d: run_dim(d, "cuda:0", args.block, args.blocks, args.warmup)
+    run = run_dim_weighted if args.weighted else run_dim
+    results = {d: run(d, "cuda:0", args.block, args.blocks, args.warmup)
                for d in args.dims}
     if args.out:
         with open(args.out, "w") as f:
-            f.write(to_markdown(results, args))
-    print(json.dumps({"bench": "multihot_pool", "results": results}))
+            f.write((to_markdown_weighted if args.weighted
+                     else to_markdown)(results, args))
+    print(json.dumps({"bench": "multihot_pool_weighted" if args.weighted
+                      else "multihot_pool", "results": results}))
 
 
 if __name__ == "__main__":
