@@ -32,7 +32,7 @@ from typing import Optional
 
 import torch
 
-from .variable import VariableMeta
+from .variable import VariableMeta, VariableShard
 from .variable_gpu import HipVariableShard
 
 
@@ -176,6 +176,19 @@ class HipTieredVariableShard(HipVariableShard):
             self.ext.gather_host(keys, slots, self.host_tk, self.host_tv,
                                  self._host_weights, out)
         return out
+
+    # ShardedVariable.pull_pooled keeps this shard on its unfused route
+    fused_pooled_readonly = False
+
+    def pull_pooled_readonly(self, values: torch.Tensor,
+                             offsets: torch.Tensor, mode: str,
+                             weights: torch.Tensor = None) -> torch.Tensor:
+        """Unfused on purpose: a row of this shard may live in host DRAM,
+        which the fused ``pool_lookup`` kernel (HBM slab only) cannot see.
+        ``pull_readonly`` above merges both tiers, then the identity pool
+        runs — the torch form of the base class."""
+        return VariableShard.pull_pooled_readonly(self, values, offsets,
+                                                  mode, weights)
 
     def update_weights(self) -> None:
         super().update_weights()

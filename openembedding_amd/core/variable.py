@@ -226,6 +226,24 @@ class VariableShard:
         out[hit] = self.weights[slots[hit]]
         return out
 
+    def pull_pooled_readonly(self, values: torch.Tensor,
+                             offsets: torch.Tensor, mode: str,
+                             weights: torch.Tensor = None) -> torch.Tensor:
+        """Read-only pooled pull over ragged bags (inference / serving):
+        values int64 [nnz_cap] keys (duplicates and the reserved key -1
+        allowed), offsets int64 [B+1], mode "sum" | "mean" | "sqrtn",
+        optional per-sample weights [nnz_cap] -> [B, dim]. A missing key is
+        a zero row that still counts toward its bag's length; the table is
+        untouched. This torch form — ``pull_readonly`` then the identity
+        pool — is the CPU path and the oracle of the fused GPU kernel."""
+        from ..ops import dispatch as ops
+        rows = self.pull_readonly(values)
+        if weights is None:
+            return ops.pool_fwd(rows, None, None, offsets, mode, False)[0]
+        return ops.pool_fwd_weighted(rows, None, None, offsets,
+                                     weights.to(rows.dtype).contiguous(),
+                                     mode)[0]
+
     def push(self, keys: torch.Tensor, grads: torch.Tensor,
              counts: torch.Tensor) -> None:
         """Queue a pre-aggregated gradient block (keys unique within block,

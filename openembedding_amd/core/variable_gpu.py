@@ -72,6 +72,9 @@ class HipVariableShard(VariableShard):
 
     INITIAL_TABLE_CAP = 1 << 16
     INITIAL_ROW_CAP = 1 << 14
+    # every row lives in the HBM slab, so pull_pooled_readonly is one fused
+    # launch (the capacity tier turns this off)
+    fused_pooled_readonly = True
 
     def __init__(self, meta: VariableMeta, shard_id: int = 0, shard_num: int = 1,
                  device: str = "cuda", seed: int = 0):
@@ -266,6 +269,30 @@ class HipVariableShard(VariableShard):
                                     torch.empty(0, dtype=self.dtype,
                                                 device=self.device), True,
                                     None)
+
+    def pull_pooled_readonly(self, values: torch.Tensor,
+                             offsets: torch.Tensor, mode: str,
+                             weights: torch.Tensor = None) -> torch.Tensor:
+        """Fused read-only pooled pull: ONE ``pool_lookup`` launch from keys
+        to [B, dim] — the probe (hash) or slot test (array) runs inside the
+        pooling kernel, so there is no unique, no slots tensor, no
+        [nnz, dim] tensor and no host sync (hipGraph-capturable). Same
+        result as the base class's torch form."""
+        from ..ops.dispatch import POOL_MODES
+        if mode not in POOL_MODES:
+            raise ValueError(f"unknown pooling mode {mode!r}")
+        if weights is not None:
+            weights = weights.to(self.dtype).contiguous()
+        values = values.contiguous()
+        offsets = offsets.contiguous()
+        if self.meta.use_hash_table:
+            return self.ext.pool_lookup(self.weights, values, offsets,
+                                        POOL_MODES[mode], weights,
+                                        tk=self.tk, tv=self.tv)
+        return self.ext.pool_lookup(self.weights, values, offsets,
+                                    POOL_MODES[mode], weights,
+                                    valid=self.valid_u8,
+                                    shard_num=self.shard_num)
 
     def update_weights(self) -> None:
         if not self._pending and not self._pending_bounded:

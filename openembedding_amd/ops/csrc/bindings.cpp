@@ -55,6 +55,9 @@ void emb_pool_wgrad(const float*, long, long, const i64*, long, const void*,
                     int, long, const float*, const int*, const float*,
                     const float*, const float*, long, int, float*,
                     hipStream_t_);
+void emb_pool_lookup(const float*, long, long, const i64*, long, const i64*,
+                     long, int, const float*, const u64*, const int*, long,
+                     const unsigned char*, long, float*, hipStream_t_);
 void emb_apply_optimizer(int, float*, float*, long, long, const i64*, long,
                          const float*, const u64*, const float*, const int*,
                          hipStream_t_);
@@ -554,6 +557,82 @@ torch::Tensor pool_wgrad(torch::Tensor rows, OptTensor inverse, OptTensor map,
                    grad_out.data_ptr<float>(), out.size(0), (int)mode,
                    dw.data_ptr<float>(), cur_stream());
     return dw;
+}
+
+// Read-only pooled lookup: table rows [R, dim] f32, values int64 [nnz_cap]
+// keys, offsets int64 [B+1], optional weights f32 [nnz_cap] -> out [B, dim]
+// in one launch, the table only read. Exactly one of (tk, tv) — the hash
+// table, int64 / int32 [cap], cap a power of two — or (valid uint8 [cap],
+// shard_num) — the array table — names the key -> row resolution.
+torch::Tensor pool_lookup(torch::Tensor rows, torch::Tensor values,
+                          torch::Tensor offsets, int64_t mode,
+                          OptTensor weights, OptTensor tk, OptTensor tv,
+                          OptTensor valid, int64_t shard_num) {
+    CHECK_GPU(rows); CHECK_CONT(rows);
+    CHECK_GPU(values); CHECK_CONT(values);
+    CHECK_GPU(offsets); CHECK_CONT(offsets);
+    TORCH_CHECK(rows.dtype() == torch::kFloat32 && rows.dim() == 2
+                && rows.size(1) >= 1,
+                "pool_lookup: rows must be float32 [R, dim >= 1]");
+    TORCH_CHECK(values.dtype() == torch::kInt64 && values.dim() == 1,
+                "pool_lookup: values must be int64 [nnz]");
+    TORCH_CHECK(offsets.dtype() == torch::kInt64 && offsets.dim() == 1
+                && offsets.numel() >= 1,
+                "pool_lookup: offsets must be int64 [B+1]");
+    TORCH_CHECK(mode >= 0 && mode <= 2, "pool_lookup: bad mode");
+    TORCH_CHECK(values.device() == rows.device()
+                && offsets.device() == rows.device(),
+                "pool_lookup: values and offsets must be on the table's "
+                "device");
+    long nnz = values.numel();
+    const float* w_ptr = nullptr;
+    if (weights.has_value()) {
+        CHECK_GPU(*weights); CHECK_CONT(*weights);
+        TORCH_CHECK(weights->dtype() == torch::kFloat32
+                    && weights->dim() == 1 && weights->numel() == nnz
+                    && weights->device() == rows.device(),
+                    "pool_lookup: weights must be float32 [nnz]");
+        w_ptr = weights->data_ptr<float>();
+    }
+    const bool hash = tk.has_value() || tv.has_value();
+    TORCH_CHECK(hash != valid.has_value(),
+                "pool_lookup: pass either (tk, tv) or (valid, shard_num)");
+    const u64* tk_ptr = nullptr;
+    const int* tv_ptr = nullptr;
+    const uint8_t* valid_ptr = nullptr;
+    long cap = 0;
+    if (hash) {
+        TORCH_CHECK(tk.has_value() && tv.has_value(),
+                    "pool_lookup: tk and tv go together");
+        CHECK_GPU(*tk); CHECK_CONT(*tk);
+        CHECK_GPU(*tv); CHECK_CONT(*tv);
+        cap = tk->numel();
+        TORCH_CHECK(tk->dtype() == torch::kInt64
+                    && tv->dtype() == torch::kInt32 && tv->numel() == cap
+                    && cap >= 1 && (cap & (cap - 1)) == 0
+                    && tk->device() == rows.device()
+                    && tv->device() == rows.device(),
+                    "pool_lookup: tk int64 / tv int32 [cap], cap a power "
+                    "of two");
+        tk_ptr = (const u64*)tk->data_ptr<i64>();
+        tv_ptr = tv->data_ptr<int>();
+    } else {
+        CHECK_GPU(*valid); CHECK_CONT(*valid);
+        cap = valid->numel();
+        TORCH_CHECK(valid->dtype() == torch::kUInt8
+                    && valid->device() == rows.device(),
+                    "pool_lookup: valid must be uint8 [cap]");
+        TORCH_CHECK(shard_num >= 1, "pool_lookup: shard_num must be >= 1");
+        valid_ptr = valid->data_ptr<uint8_t>();
+    }
+    const c10::cuda::CUDAGuard guard(rows.device());
+    long B = offsets.numel() - 1;
+    auto out = torch::empty({B, rows.size(1)}, rows.options());
+    emb_pool_lookup(rows.data_ptr<float>(), rows.size(0), rows.size(1),
+                    values.data_ptr<i64>(), nnz, offsets.data_ptr<i64>(), B,
+                    (int)mode, w_ptr, tk_ptr, tv_ptr, cap, valid_ptr,
+                    (long)shard_num, out.data_ptr<float>(), cur_stream());
+    return out;
 }
 
 void mask_tail(torch::Tensor keys, torch::Tensor grads, torch::Tensor counts,
@@ -1140,6 +1219,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("bag_of"), pybind11::arg("bag_scale"),
           pybind11::arg("out"), pybind11::arg("grad_out"),
           pybind11::arg("mode"), pybind11::arg("dw") = pybind11::none());
+    m.def("pool_lookup", &pool_lookup,
+          "read-only pooled lookup, keys -> pooled rows in one launch "
+          "(hash: tk/tv; array: valid/shard_num)",
+          pybind11::arg("rows"), pybind11::arg("values"),
+          pybind11::arg("offsets"), pybind11::arg("mode"),
+          pybind11::arg("weights") = pybind11::none(),
+          pybind11::arg("tk") = pybind11::none(),
+          pybind11::arg("tv") = pybind11::none(),
+          pybind11::arg("valid") = pybind11::none(),
+          pybind11::arg("shard_num") = 1);
     m.def("apply_optimizer", &apply_optimizer, "fused sparse optimizer step");
     m.def("mask_tail", &mask_tail,
           "zero the garbage tail of a bounded block (enables multi-block "

@@ -565,45 +565,84 @@ DEV long pool_row(long j, long e, const i64* __restrict__ inverse,
     return (row >= 0 && row < R) ? row : -1;
 }
 
-template <int G, int PF_CF, int PF_ILP, typename MapT,
-          bool WEIGHTED = false>
-__global__ void k_pool_fwd(const float* __restrict__ rows, long R, long dim,
-                           const i64* __restrict__ inverse, long nnz,
-                           const MapT* __restrict__ map, long u,
-                           const i64* __restrict__ offsets, long B, int mode,
-                           float* __restrict__ out,
-                           int* __restrict__ bag_of,
-                           const float* __restrict__ weights,
-                           float* __restrict__ bag_scale) {
-    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (bag_of) {
-        const long nthreads = (long)gridDim.x * blockDim.x;
-        for (long j = pool_clamp(offsets[B], nnz) + tid; j < nnz;
-             j += nthreads)
-            bag_of[j] = -1;
+// Resolver policies of pool_accumulate: element j of a bag ending at e ->
+// row of ``rows``, -1 = zero row. PoolChain is the training chain above.
+template <typename MapT>
+struct PoolChain {
+    const i64* __restrict__ inverse;
+    const MapT* __restrict__ map;
+    long nidx, R;
+    __device__ __forceinline__ long operator()(long j, long e) const {
+        return pool_row(j, e, inverse, map, nidx, R);
     }
-    const long b = tid / G;
-    const int lane = threadIdx.x % G;
-    if (b >= B) return;
-    const long s = pool_clamp(offsets[b], nnz);
-    long e = pool_clamp(offsets[b + 1], nnz);
-    if (e < s) e = s;
+};
+
+// Read-only key -> row resolution inside the gather (k_pool_lookup): the
+// insert == 0 probe of k_ht_lookup — same hash, EMPTY rule and probe bound,
+// no CAS, nothing written. Key -1 and a tv value outside [0, R) are misses.
+struct PoolHashKeys {
+    const i64* __restrict__ values;
+    const u64* __restrict__ tk;
+    const int* __restrict__ tv;
+    long mask, R;
+    __device__ __forceinline__ long operator()(long j, long e) const {
+        if (j >= e) return -1;
+        const u64 k = (u64)values[j];
+        if (k == EMPTY) return -1;
+        u64 h = splitmix64(k) & (u64)mask;
+        for (long p = 0; p <= mask; ++p) {
+            const u64 cur = tk[h];
+            if (cur == k) {
+                const long row = (long)tv[h];
+                return (row >= 0 && row < R) ? row : -1;
+            }
+            if (cur == EMPTY) return -1;
+            h = (h + 1) & (u64)mask;
+        }
+        return -1;
+    }
+};
+
+// array table: slot = key / shard_num (k_array_touch's layout), a hit only
+// for 0 <= key, slot < cap and a live row
+struct PoolArrayKeys {
+    const i64* __restrict__ values;
+    const unsigned char* __restrict__ valid;
+    long shard_num, cap, R;
+    __device__ __forceinline__ long operator()(long j, long e) const {
+        if (j >= e) return -1;
+        const i64 k = values[j];
+        if (k < 0) return -1;
+        const i64 slot = k / shard_num;
+        if (slot >= cap || slot >= R) return -1;
+        return valid[slot] ? (long)slot : -1;
+    }
+};
+
+// The accumulate body shared by k_pool_fwd and k_pool_lookup: the G-lane
+// group of ``lane`` pools elements [s, e) into out[b], resolving element
+// rows through ``resolve``. ``bag_scale`` (WEIGHTED only) may be null.
+template <int G, int PF_CF, int PF_ILP, bool WEIGHTED, typename Resolve>
+DEV void pool_accumulate(const float* __restrict__ rows, long dim, long s,
+                         long e, long b, int lane, int mode,
+                         const float* __restrict__ weights,
+                         float* __restrict__ out,
+                         float* __restrict__ bag_scale,
+                         const Resolve& resolve) {
     float scale = 1.0f;
     if constexpr (!WEIGHTED) scale = pool_scale(mode, e - s);
-    const long nidx = map ? u : R;   // valid range of an inverse value
     for (long c0 = 0; c0 < dim; c0 += (long)G * PF_CF) {
         float acc[PF_CF];
         #pragma unroll
         for (int k = 0; k < PF_CF; ++k) acc[k] = 0.0f;
-        long myrow = pool_row(s + lane, e, inverse, map, nidx, R);
+        long myrow = resolve(s + lane, e);
         // WEIGHTED only: this lane's element weight and the bag's
         // denominator (every column pass recomputes the same value)
         float myw = 0.0f, den = 0.0f;
         if constexpr (WEIGHTED)
             if (s + lane < e) myw = weights[s + lane];
         for (long j0 = s; j0 < e; j0 += G) {
-            const long nextrow = pool_row(j0 + G + lane, e, inverse, map,
-                                          nidx, R);
+            const long nextrow = resolve(j0 + G + lane, e);
             float nextw = 0.0f;
             if constexpr (WEIGHTED)
                 if (j0 + G + lane < e) nextw = weights[j0 + G + lane];
@@ -647,7 +686,7 @@ __global__ void k_pool_fwd(const float* __restrict__ rows, long R, long dim,
         }
         if constexpr (WEIGHTED) {
             scale = pool_wscale(mode, den);
-            if (c0 == 0 && lane == 0) bag_scale[b] = scale;
+            if (bag_scale && c0 == 0 && lane == 0) bag_scale[b] = scale;
         }
         #pragma unroll
         for (int k = 0; k < PF_CF; ++k) {
@@ -655,8 +694,64 @@ __global__ void k_pool_fwd(const float* __restrict__ rows, long R, long dim,
             if (c < dim) out[(u64)b * dim + c] = acc[k] * scale;
         }
     }
+}
+
+template <int G, int PF_CF, int PF_ILP, typename MapT,
+          bool WEIGHTED = false>
+__global__ void k_pool_fwd(const float* __restrict__ rows, long R, long dim,
+                           const i64* __restrict__ inverse, long nnz,
+                           const MapT* __restrict__ map, long u,
+                           const i64* __restrict__ offsets, long B, int mode,
+                           float* __restrict__ out,
+                           int* __restrict__ bag_of,
+                           const float* __restrict__ weights,
+                           float* __restrict__ bag_scale) {
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (bag_of) {
+        const long nthreads = (long)gridDim.x * blockDim.x;
+        for (long j = pool_clamp(offsets[B], nnz) + tid; j < nnz;
+             j += nthreads)
+            bag_of[j] = -1;
+    }
+    const long b = tid / G;
+    const int lane = threadIdx.x % G;
+    if (b >= B) return;
+    const long s = pool_clamp(offsets[b], nnz);
+    long e = pool_clamp(offsets[b + 1], nnz);
+    if (e < s) e = s;
+    const long nidx = map ? u : R;   // valid range of an inverse value
+    const PoolChain<MapT> resolve{inverse, map, nidx, R};
+    pool_accumulate<G, PF_CF, PF_ILP, WEIGHTED>(rows, dim, s, e, b, lane,
+                                                 mode, weights, out,
+                                                 bag_scale, resolve);
     if (bag_of)
         for (long j = s + lane; j < e; j += G) bag_of[j] = (int)b;
+}
+
+// Read-only pooled lookup (inference / serving): values [nnz] int64 keys
+// and offsets [B+1] straight to out [B, dim]. The latency plan, the scale
+// (taken from offsets only, so a missed element still counts toward the
+// bag length) and the element-order plain adds are k_pool_fwd's — the two
+// kernels share pool_accumulate — but "resolve" is key -> row inside the
+// kernel (PoolHashKeys / PoolArrayKeys): no unique, no inverse, no slots
+// tensor, and the table is only read. A miss adds a zero row; an empty bag
+// or one with offsets[b+1] < offsets[b] is zeros.
+template <int G, int PF_CF, int PF_ILP, bool WEIGHTED, typename Resolve>
+__global__ void k_pool_lookup(const float* __restrict__ rows, long dim,
+                              long nnz, const i64* __restrict__ offsets,
+                              long B, int mode,
+                              const float* __restrict__ weights,
+                              float* __restrict__ out, Resolve resolve) {
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long b = tid / G;
+    const int lane = threadIdx.x % G;
+    if (b >= B) return;
+    const long s = pool_clamp(offsets[b], nnz);
+    long e = pool_clamp(offsets[b + 1], nnz);
+    if (e < s) e = s;
+    pool_accumulate<G, PF_CF, PF_ILP, WEIGHTED>(rows, dim, s, e, b, lane,
+                                                 mode, weights, out, nullptr,
+                                                 resolve);
 }
 
 // -------------------------------------------------------- reduce-by-inverse
@@ -1553,6 +1648,26 @@ static void pool_dispatch(const float* rows, long R, long dim,
 #undef LAUNCH_POOL
 }
 
+// the same ladder for the read-only lookup; Resolve is the key -> row policy
+template <bool WEIGHTED, typename Resolve>
+static void pool_lookup_dispatch(const float* rows, long dim, long nnz,
+                                 const i64* offsets, long B, int mode,
+                                 const float* weights, float* out,
+                                 const Resolve& resolve,
+                                 hipStream_t stream) {
+    if (B == 0) return;
+#define LAUNCH_LOOKUP(G, CF, ILP)                                           \
+    k_pool_lookup<G, CF, ILP, WEIGHTED, Resolve>                            \
+        <<<grid1d(B * G), BLOCK, 0, stream>>>(rows, dim, nnz, offsets, B,   \
+                                              mode, weights, out, resolve)
+    if (dim <= 16) LAUNCH_LOOKUP(16, 1, 16);
+    else if (dim <= 32) LAUNCH_LOOKUP(16, 2, 8);
+    else if (dim <= 64) LAUNCH_LOOKUP(64, 1, 16);
+    else if (dim <= 128) LAUNCH_LOOKUP(64, 2, 8);
+    else LAUNCH_LOOKUP(64, 4, 4);
+#undef LAUNCH_LOOKUP
+}
+
 extern "C" {
 
 void emb_unique(const i64* keys, long n, u64* tk, int* tv, long cap,
@@ -1666,6 +1781,33 @@ void emb_pool_fwd_weighted(const float* rows, long R, long dim,
     pool_dispatch<true>(rows, R, dim, inverse, nnz, map, map_kind, u,
                         offsets, B, mode, out, bag_of, weights, bag_scale,
                         stream);
+}
+
+// read-only pooled lookup, values -> out in one launch. tk != null: hash
+// table (tk/tv, cap a power of two); else array table (valid [cap],
+// shard_num >= 1). weights null = plain pool.
+void emb_pool_lookup(const float* rows, long R, long dim, const i64* values,
+                     long nnz, const i64* offsets, long B, int mode,
+                     const float* weights, const u64* tk, const int* tv,
+                     long cap, const unsigned char* valid, long shard_num,
+                     float* out, hipStream_t stream) {
+    if (tk) {
+        const PoolHashKeys r{values, tk, tv, cap - 1, R};
+        if (weights)
+            pool_lookup_dispatch<true>(rows, dim, nnz, offsets, B, mode,
+                                       weights, out, r, stream);
+        else
+            pool_lookup_dispatch<false>(rows, dim, nnz, offsets, B, mode,
+                                        nullptr, out, r, stream);
+    } else {
+        const PoolArrayKeys r{values, valid, shard_num, cap, R};
+        if (weights)
+            pool_lookup_dispatch<true>(rows, dim, nnz, offsets, B, mode,
+                                       weights, out, r, stream);
+        else
+            pool_lookup_dispatch<false>(rows, dim, nnz, offsets, B, mode,
+                                        nullptr, out, r, stream);
+    }
 }
 
 // weighted pooled backward: element e's factor is

@@ -74,8 +74,10 @@ class PullHandle:
     EmbeddingPullOperator.cpp:67-79,229-249)."""
 
     shape: torch.Size
-    unique: torch.Tensor            # [u] unique keys, local order
-    inverse: torch.Tensor           # [n] position -> unique id
+    # [u] unique keys, local order, and [n] position -> unique id; both
+    # None on the fused read-only pooled pull, which dedups nothing
+    unique: Optional[torch.Tensor] = None
+    inverse: Optional[torch.Tensor] = None
     order: Optional[torch.Tensor] = None       # [u] perm grouping unique by owner
     send_splits: Optional[List[int]] = None    # keys sent to each rank
     recv_splits: Optional[List[int]] = None    # keys received from each rank
@@ -227,8 +229,13 @@ class ShardedVariable:
         are never used. ``wgrad`` says the matching ``push_pooled`` will be
         asked for the weights' gradient.
 
-        Single GPU: fused — no [nnz, dim] tensor, zero host syncs. Every
-        other route pools its flat pull output. Collective like ``pull``."""
+        Single GPU: fused — no [nnz, dim] tensor, zero host syncs; with
+        ``readonly`` (and no ``pre``, no capacity tier) that is one
+        ``pool_lookup`` launch that resolves keys inside the pooling kernel,
+        and the handle then carries only ``shape``. A key missing from the
+        table reads as a zero row and still counts toward its bag's length.
+        Every other route pools its flat pull output. Collective like
+        ``pull``."""
         flat = values.reshape(-1).to(torch.int64)
         dim = self.shard.dim
         gpu = getattr(self.shard, "pull_bounded", None) is not None
@@ -250,6 +257,16 @@ class ShardedVariable:
                            bounded=True, u_dev=u_dev, slots=slots,
                            bag_of=bag_of, bag_scale=bag_scale)
             return out, h
+        if (gpu and not remote and readonly and pre is None
+                and getattr(self.shard, "fused_pooled_readonly", False)):
+            # inference: one fused launch from keys to pooled rows — no
+            # dedup (nothing is written, so it buys nothing), no
+            # [nnz, dim] tensor, no host sync; capturable like training.
+            # Nothing runs backward, so the handle carries only the shape.
+            self.stat_pull_indices += flat.numel()
+            out = self.shard.pull_pooled_readonly(flat, offsets, mode,
+                                                  weights)
+            return out, PullHandle(shape=flat.shape)
         if pre is None:
             if not gpu:
                 # the torch engine rejects the reserved key -1 loudly; a

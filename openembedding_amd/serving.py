@@ -57,6 +57,60 @@ class ServedVariable:
         out = self.shard.pull_readonly(flat)
         return out.view(*indices.shape, self.shard.dim)
 
+    def pull_pooled(self, values, offsets, mode: str = "sum",
+                    per_sample_weights=None) -> torch.Tensor:
+        """Pooled read of ragged bags, the serving side of ``EmbeddingBag``:
+        bag b combines the rows of ``values[offsets[b]:offsets[b+1]]`` with
+        ``mode`` ("sum" | "mean" | "sqrtn") and, when given, the per-sample
+        weights (TF ``embedding_lookup_sparse`` rules) -> [B, dim]. A key
+        missing from the table is a zero row that still counts toward its
+        bag's length. On a GPU table this is one fused kernel launch.
+
+        Serving input is untrusted, so everything is validated on the host
+        before any launch; a violation raises ``ValueError``."""
+        from .ops.dispatch import POOL_MODES
+        if mode not in POOL_MODES:
+            raise ValueError(f"mode must be one of {sorted(POOL_MODES)}, "
+                             f"got {mode!r}")
+        try:
+            vals = torch.as_tensor(values).detach().cpu()
+            off = torch.as_tensor(offsets).detach().cpu()
+        except (TypeError, ValueError, RuntimeError) as e:
+            raise ValueError(f"values/offsets are not integer lists: {e}")
+        if vals.numel() == 0:
+            vals = vals.to(torch.int64)
+        if vals.dim() != 1 or vals.is_floating_point() \
+                or vals.is_complex() or vals.dtype == torch.bool:
+            raise ValueError("values must be a 1-D list of integer ids")
+        if off.dim() != 1 or off.numel() < 1 or off.is_floating_point() \
+                or off.is_complex() or off.dtype == torch.bool:
+            raise ValueError("offsets must be a 1-D list of B+1 integer "
+                             "row splits")
+        vals = vals.to(torch.int64)
+        off = off.to(torch.int64)
+        if int(off[0]) != 0 or bool((off[1:] < off[:-1]).any()) \
+                or int(off[-1]) > vals.numel():
+            raise ValueError("offsets must start at 0, be non-decreasing "
+                             f"and end at or below len(values)="
+                             f"{vals.numel()}")
+        w = None
+        if per_sample_weights is not None:
+            try:
+                w = torch.as_tensor(per_sample_weights).detach().cpu()
+                w = w.to(self.shard.dtype)
+            except (TypeError, ValueError, RuntimeError) as e:
+                raise ValueError(f"per_sample_weights are not numbers: {e}")
+            if w.dim() != 1 or w.numel() != vals.numel():
+                raise ValueError("per_sample_weights must have len(values)="
+                                 f"{vals.numel()} elements, got "
+                                 f"{tuple(w.shape)}")
+            if not bool(torch.isfinite(w).all()):
+                raise ValueError("per_sample_weights must be finite")
+            w = w.to(self.shard.device)
+        dev = self.shard.device
+        return self.shard.pull_pooled_readonly(vals.to(dev), off.to(dev),
+                                               mode, w)
+
 
 class ServedModel:
     """One loaded model: meta + read-only variables keyed by variable_id."""
@@ -364,6 +418,21 @@ class ServingClient:
                           {"indices": indices})
         return r["weights"]
 
+    def pull_pooled(self, sign: str, variable_id: int, values, offsets,
+                    mode: str = "sum", per_sample_weights=None) -> List:
+        """Pooled rows [B][dim] of ragged bags (``ServedVariable.
+        pull_pooled``), with the replica failover of ``pull``."""
+        body = {"values": values, "offsets": offsets, "mode": mode}
+        if per_sample_weights is not None:
+            body["per_sample_weights"] = per_sample_weights
+        for k, v in body.items():
+            if torch.is_tensor(v):
+                body[k] = v.tolist()
+        r = self._request(
+            "POST", f"/models/{sign}/variables/{variable_id}/pull_pooled",
+            body)
+        return r["pooled"]
+
     def show_models(self) -> List[dict]:
         return self._request("GET", "/models")
 
@@ -378,9 +447,14 @@ def make_app(controller: Optional[ModelController] = None,
       GET    /nodes             list nodes
       DELETE /nodes/{id}        request shutdown
       POST   /models/{sign}/variables/{vid}/pull   {"indices": [[...]]}
-    The pull route is an addition over the reference (whose serving data path
-    went through TF-Serving custom ops): it makes the server usable from any
-    HTTP client without TF."""
+      POST   /models/{sign}/variables/{vid}/pull_pooled
+             {"values": [...], "offsets": [...], "mode": "sum"|"mean"|"sqrtn",
+              "per_sample_weights"?: [...]} -> {"pooled": [[...]]}
+    The pull routes are an addition over the reference (whose serving data
+    path went through TF-Serving custom ops): they make the server usable
+    from any HTTP client without TF. pull_pooled is the read side of
+    EmbeddingBag: the combiner runs on the server, so a client fetches
+    B x dim floats instead of nnz x dim; 422 on malformed bags."""
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
 
@@ -398,6 +472,12 @@ def make_app(controller: Optional[ModelController] = None,
 
     class PullReq(BaseModel):
         indices: list
+
+    class PullPooledReq(BaseModel):
+        values: list
+        offsets: list
+        mode: str = "sum"
+        per_sample_weights: Optional[list] = None
 
     @app.post("/models")
     def create_model(req: CreateModelReq):
@@ -489,6 +569,21 @@ def make_app(controller: Optional[ModelController] = None,
         idx = torch.tensor(req.indices, dtype=torch.int64)
         out = var.pull_weights(idx)
         return {"weights": out.cpu().tolist()}
+
+    @app.post("/models/{sign}/variables/{variable_id}/pull_pooled")
+    def pull_pooled(sign: str, variable_id: int, req: PullPooledReq):
+        try:
+            var = controller.manager.find_model_variable(sign, variable_id)
+        except KeyError as e:
+            raise HTTPException(status_code=404, detail=str(e))
+        except RuntimeError as e:
+            raise HTTPException(status_code=409, detail=str(e))
+        try:
+            out = var.pull_pooled(req.values, req.offsets, req.mode,
+                                  req.per_sample_weights)
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        return {"pooled": out.cpu().tolist()}
 
     return app
 

@@ -3,6 +3,8 @@
     python scripts/bench_multihot.py [--out profiles/multihot_pool.md]
     python scripts/bench_multihot.py --weighted \
         [--out profiles/multihot_pool_weighted.md]
+    python scripts/bench_multihot.py --readonly \
+        [--out profiles/multihot_pool_readonly.md]
 
 fused    : EmbeddingBag forward (pooled pull) + backward (pooled push) +
            commit — no [nnz, dim] tensor in either direction.
@@ -18,6 +20,11 @@ bag's sum of w). Both are timed with data weights (no gradient) and with
 weights that require a gradient (``_wg``: the fused step adds k_pool_wgrad,
 the composed step autograd's [nnz, dim] product backward), and the unweighted
 fused step runs in the same alternating blocks for reference.
+
+``--readonly`` times evaluation instead of training (see
+``run_dim_readonly``): the fused read-only pooled lookup against the flat
+read-only pull plus ``ops.pool_fwd``, both eager, and the fused lookup as a
+captured hipGraph.
 
 Workload: batch 4096 bags, mean length 8 with a long tail (lengths drawn
 multinomially from log-normal weights, so every batch has the same nnz and
@@ -256,6 +263,121 @@ def to_markdown_weighted(results, args):
     return "\n".join(lines) + "\n"
 
 
+def run_dim_readonly(dim, device, block, blocks, warmup):
+    """Evaluation (no_grad) lookup of the same workload: the fused
+    read-only pooled lookup against the route evaluation took before it —
+    flat ``pull(readonly=True)`` (exact unique with its host sync, row
+    gather, index_select to [nnz, dim]) plus ``ops.pool_fwd``. Both eager;
+    the fused lookup also as a captured hipGraph (the flat route syncs the
+    host and cannot be captured)."""
+    import openembedding_amd.context as cm
+    import openembedding_amd.torch as api
+    from openembedding_amd.ops import dispatch as ops
+    if cm._context is not None:
+        cm._context.finalize()
+        cm._context = None
+    api._tracked.clear()
+    batches = make_batches(device)
+    fused_step, _, bag, _ = build(dim, device)
+    for vals, offsets, _ in batches:        # every timed key gets a row
+        fused_step(vals, offsets)
+    bag.eval()
+    sharded = bag.variable.sharded
+
+    def fused(vals, offsets):
+        with torch.no_grad():
+            return bag(vals, offsets)
+
+    def flat_route(vals, offsets):
+        with torch.no_grad():
+            rows, _ = sharded.pull(vals, readonly=True)
+            return ops.pool_fwd(rows.reshape(-1, dim), None, None, offsets,
+                                "mean")[0]
+
+    for vals, offsets, _ in batches:        # same rows, same order: same bits
+        assert torch.equal(fused(vals, offsets), flat_route(vals, offsets))
+
+    eager = {"fused": lambda i: fused(*batches[i % N_BATCHES][:2]),
+             "flat": lambda i: flat_route(*batches[i % N_BATCHES][:2])}
+    for i in range(warmup):
+        for fn in eager.values():
+            fn(i)
+    torch.cuda.synchronize()
+    res = {"eager": summarize(time_blocks(eager, batches, block, blocks))}
+
+    s_vals = batches[0][0].clone()
+    s_off = batches[0][1].clone()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            fused(s_vals, s_off)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = fused(s_vals, s_off)
+
+    def replay(i):
+        vals, offsets, _ = batches[i % N_BATCHES]
+        s_vals.copy_(vals)
+        s_off.copy_(offsets)
+        graph.replay()
+
+    replay(1)
+    assert torch.equal(out, fused(*batches[1][:2]))
+    for i in range(warmup):
+        replay(i)
+    torch.cuda.synchronize()
+    res["graph"] = summarize(time_blocks({"fused": replay}, batches, block,
+                                         blocks))
+    res["max_bag_len"] = max(b[2] for b in batches)
+    res["flat_over_fused_eager"] = (res["eager"]["flat"]["median_us"]
+                                    / res["eager"]["fused"]["median_us"])
+    res["flat_eager_over_fused_graph"] = (
+        res["eager"]["flat"]["median_us"]
+        / res["graph"]["fused"]["median_us"])
+    return res
+
+
+def to_markdown_readonly(results, args):
+    cell = lambda r: (f"{r['median_us']:.1f} ({r['p10_us']:.1f}-"
+                      f"{r['p90_us']:.1f})")
+    lines = [
+        "# Read-only pooled lookup: fused vs flat pull + pool (MI355X)",
+        "",
+        f"`scripts/bench_multihot.py --readonly --block {args.block} "
+        f"--blocks {args.blocks}`: batch {B} bags, nnz "
+        f"{B * MEAN_LEN} (mean length {MEAN_LEN}, long tail), array table "
+        f"of {VOCAB} rows trained one step per batch first (every looked-up "
+        "key has a row), mode mean, under `torch.no_grad()`. `fused` is "
+        "EmbeddingBag evaluation (one `k_pool_lookup` launch); `flat` is "
+        "the route evaluation took before: `pull(readonly=True)` (exact "
+        "unique with a host sync, row gather, index_select to [nnz, dim]) "
+        "then `ops.pool_fwd`. Per-call time from device events around "
+        f"alternating blocks of {args.block} calls, {args.blocks} blocks per "
+        f"path after {args.warmup} warm-up calls, same process, same "
+        "batches; median (p10-p90) in microseconds. `fused graph` replays "
+        "one captured hipGraph (plus the two input copies); the flat route "
+        "syncs the host and cannot be captured. Outputs of the two routes "
+        "are checked bit-equal before timing.",
+        "",
+        "| dim | fused eager | flat eager | flat / fused (eager) | "
+        "fused graph | flat eager / fused graph |",
+        "|---|---|---|---|---|---|",
+    ]
+    for dim, r in results.items():
+        lines.append(
+            f"| {dim} | {cell(r['eager']['fused'])} | "
+            f"{cell(r['eager']['flat'])} | "
+            f"{r['flat_over_fused_eager']:.2f}x | "
+            f"{cell(r['graph']['fused'])} | "
+            f"{r['flat_eager_over_fused_graph']:.2f}x |")
+    lines.append("")
+    lines.append("Longest bag over the batches: "
+                 f"{max(r['max_bag_len'] for r in results.values())}.")
+    return "\n".join(lines) + "\n"
+
+
 def time_blocks(steps, batches, block, blocks):
     """steps: {name: callable(i)} timed in alternating blocks."""
     ms = {k: [] for k in steps}
@@ -392,20 +514,29 @@ def main():
     ap.add_argument("--weighted", action="store_true",
                     help="time the per-sample-weight step (with and "
                          "without a gradient for the weights)")
+    ap.add_argument("--readonly", action="store_true",
+                    help="time the evaluation lookup: fused read-only "
+                         "pooled lookup vs flat pull(readonly) + pool_fwd")
     args = ap.parse_args()
+    if args.weighted and args.readonly:
+        sys.exit("--weighted and --readonly are separate measurements")
     if not torch.cuda.is_available():
         sys.exit("bench_multihot.py needs a GPU (no CPU fallback)")
     from openembedding_amd.ops import require_hip
     require_hip()
-    run = run_dim_weighted if args.weighted else run_dim
+    name, run, md = "multihot_pool", run_dim, to_markdown
+    if args.weighted:
+        name, run, md = ("multihot_pool_weighted", run_dim_weighted,
+                         to_markdown_weighted)
+    elif args.readonly:
+        name, run, md = ("multihot_pool_readonly", run_dim_readonly,
+                         to_markdown_readonly)
     results = {d: run(d, "cuda:0", args.block, args.blocks, args.warmup)
                for d in args.dims}
     if args.out:
         with open(args.out, "w") as f:
-            f.write((to_markdown_weighted if args.weighted
-                     else to_markdown)(results, args))
-    print(json.dumps({"bench": "multihot_pool_weighted" if args.weighted
-                      else "multihot_pool", "results": results}))
+            f.write(md(results, args))
+    print(json.dumps({"bench": name, "results": results}))
 
 
 if __name__ == "__main__":
