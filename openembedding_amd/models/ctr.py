@@ -64,18 +64,31 @@ class _FusedMLP3Fn(torch.autograd.Function):
     def forward(ctx, x0, partial, w1, b1, w2, b2, w3, b3, w4, b4, bufs):
         from ..ops import require_hip
         ext = require_hip()
-        # refresh padded weight copies (zero tails allocated once in bufs)
-        # in ONE launch — three aten copy_ were ~3.8 us of launch/ramp
-        # each for <1 MB moved (profiles/step_attrib_r2.txt)
-        ext.mlp3_pack(w1, bufs["w1p"], False, w2, bufs["w2p"], False,
-                      w3, bufs["w3p"], False)
+        # refresh the padded weight images in ONE launch per step: the
+        # kernels stream them in the fragment-major layout (mlp.hip), pads
+        # written by the pack itself. When a backward will follow, the
+        # three transposed dgrad operands are packed here too — the
+        # weights saved for backward cannot change before it runs, so the
+        # copies are the weights this forward used; under no_grad (eval,
+        # serving) only the three forward images are written.
+        # needs_input_grad reflects requires_grad alone and grad mode is
+        # always off in here, so the caller's grad mode comes in through
+        # bufs["grad_mode"] (_dnn_out sets it; absent = assume enabled).
+        srcs = [w1, w2, w3]
+        dsts = [bufs["w1p"], bufs["w2p"], bufs["w3p"]]
+        trans = [False, False, False]
+        if any(ctx.needs_input_grad) and bufs.get("grad_mode", True):
+            srcs += [w3, w2, w1]
+            dsts += [bufs["w3tp"], bufs["w2tp"], bufs["w1tp"]]
+            trans += [True, True, True]
+        ext.mlp3_pack_frag([w.contiguous() for w in srcs], dsts, trans)
         w4f = w4.reshape(-1).contiguous()
         # partial (the head's first-order+FM+dense logits) folds into the
         # final-dot epilogue, replacing the `partial + dnn` add kernel
         out, a1, a2, a3 = ext.mlp3_fwd(x0, bufs["w1p"], b1, bufs["w2p"], b2,
                                        bufs["w3p"], b3, w4f, b4,
                                        None if partial is None
-                                       else partial.contiguous())
+                                       else partial.contiguous(), frag=True)
         ctx.save_for_backward(x0, w1, w2, w3, w4f, a1, a2, a3)
         ctx.bufs = bufs
         ctx._params = (w1, b1, w2, b2, w3, b3, w4, b4)
@@ -89,10 +102,8 @@ class _FusedMLP3Fn(torch.autograd.Function):
         x0, w1, w2, w3, w4f, a1, a2, a3 = ctx.saved_tensors
         bufs = ctx.bufs
         K0 = w1.shape[1]
-        # padded transposed weights for the fused dgrad chain (one launch;
-        # w1tp takes w1p as source so its K0p..K0 tail rows stay zero)
-        ext.mlp3_pack(w3, bufs["w3tp"], True, w2, bufs["w2tp"], True,
-                      bufs["w1p"], bufs["w1tp"], True)
+        # the transposed fragment-major weights for the fused dgrad chain
+        # were packed by the forward, in the same launch as its own
         # prebound flat-optimizer grads? decided BEFORE the dgrad launch:
         # the dz3-assembly loop there carries the head wgrad/bias sums
         # (it reads dout and a3 anyway), killing the separate head pass
@@ -112,7 +123,7 @@ class _FusedMLP3Fn(torch.autograd.Function):
                 bufs["bscratch"] = bscratch
         dx0, dz1, dz2, dz3 = ext.mlp3_bwd(
             dout.contiguous(), a1, a2, a3, w4f,
-            bufs["w3tp"], bufs["w2tp"], bufs["w1tp"], bscratch)
+            bufs["w3tp"], bufs["w2tp"], bufs["w1tp"], bscratch, frag=True)
         # bias grads as GEMVs (fallback paths): torch's column-sum of
         # row-major bf16 ran ~16 us each (reduce_kernel); ones@dz is a
         # hipBLASLt GEMV. The default path below does them in the fused
@@ -276,6 +287,7 @@ class _CTRBase(nn.Module):
                 self._w1pad = {"w1p": z(H, K0p), "w2p": z(H, Hp),
                                "w3p": z(H, Hp), "w3tp": z(H, Hp),
                                "w2tp": z(H, Hp), "w1tp": z(K0p, Hp)}
+            self._w1pad["grad_mode"] = torch.is_grad_enabled()
             return _FusedMLP3Fn.apply(
                 deep_in, partial, l1.weight, l1.bias, l2.weight, l2.bias,
                 l3.weight, l3.bias, l4.weight, l4.bias, self._w1pad)

@@ -114,11 +114,14 @@ void emb_cin_dx(const float*, const void*, const float*, const float*,
 void emb_mlp3_fwd(const void*, long, long, const void*, const void*,
                   const void*, const void*, const void*, const void*,
                   const void*, const void*, const float*, long, long, void*,
-                  void*, void*, float*, int, hipStream_t_);
+                  void*, void*, float*, int, int, hipStream_t_);
 void emb_mlp3_bwd(const float*, long, long, const void*, const void*,
                   const void*, const void*, const void*, const void*,
                   const void*, long, long, void*, void*, void*, void*,
-                  float*, int, hipStream_t_);
+                  float*, int, int, hipStream_t_);
+void emb_mlp3_pack_frag(int, const void* const*, void* const*, const long*,
+                        const long*, const long*, const long*, const long*,
+                        const int*, hipStream_t_);
 }
 
 namespace {
@@ -1070,6 +1073,49 @@ void mlp3_pack(torch::Tensor s1, torch::Tensor d1, bool t1,
                   a[2][3], tt[2], cur_stream());
 }
 
+void mlp3_pack_frag(std::vector<torch::Tensor> srcs,
+                    std::vector<torch::Tensor> dsts,
+                    std::vector<bool> trans) {
+    // one launch writing up to six fragment-major weight images (mlp.hip).
+    // dst [N, Kp] gives the image's dimensions and is written in full;
+    // src is the [rows, cols] weight, or its transpose when trans[i]
+    const size_t n = srcs.size();
+    TORCH_CHECK(n >= 1 && n <= 6 && dsts.size() == n && trans.size() == n,
+                "mlp3_pack_frag: 1..6 matrices, lists of equal length");
+    const void* sp[6];
+    void* dp[6];
+    long rows[6], cols[6], sld[6], N[6], Kp[6];
+    int tt[6];
+    for (size_t i = 0; i < n; i++) {
+        const torch::Tensor &s = srcs[i], &d = dsts[i];
+        CHECK_GPU(s); CHECK_GPU(d); CHECK_CONT(d);
+        TORCH_CHECK(s.dtype() == torch::kBFloat16
+                    && d.dtype() == torch::kBFloat16
+                    && s.dim() == 2 && d.dim() == 2 && s.stride(1) == 1
+                    && s.stride(0) >= s.size(1)
+                    && s.device() == d.device(),
+                    "mlp3_pack_frag dtypes/shapes");
+        rows[i] = s.size(0); cols[i] = s.size(1); sld[i] = s.stride(0);
+        N[i] = d.size(0); Kp[i] = d.size(1);
+        tt[i] = trans[i];
+        TORCH_CHECK(N[i] > 0 && N[i] % 16 == 0 && Kp[i] > 0
+                    && Kp[i] % 32 == 0,
+                    "mlp3_pack_frag: dst must be [x16, x32]");
+        TORCH_CHECK((tt[i] ? cols[i] : rows[i]) <= N[i]
+                    && (tt[i] ? rows[i] : cols[i]) <= Kp[i],
+                    "mlp3_pack_frag: dst too small");
+        TORCH_CHECK(N[i] * Kp[i] < (1L << 31)
+                    && rows[i] * sld[i] < (1L << 31),
+                    "mlp3_pack_frag: 32-bit indices");
+        TORCH_CHECK((reinterpret_cast<uintptr_t>(d.data_ptr()) & 15) == 0,
+                    "mlp3_pack_frag: dst must be 16-byte aligned");
+        sp[i] = s.data_ptr(); dp[i] = d.data_ptr();
+    }
+    const c10::cuda::CUDAGuard guard(srcs[0].device());
+    emb_mlp3_pack_frag((int)n, sp, dp, rows, cols, sld, N, Kp, tt,
+                       cur_stream());
+}
+
 // ---- fused BCE-with-logits --------------------------------------------
 
 torch::Tensor bce_fwd(torch::Tensor logits, torch::Tensor labels) {
@@ -1102,9 +1148,10 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 mlp3_fwd(torch::Tensor x0, torch::Tensor w1, torch::Tensor b1,
          torch::Tensor w2, torch::Tensor b2, torch::Tensor w3,
          torch::Tensor b3, torch::Tensor w4, torch::Tensor b4,
-         c10::optional<torch::Tensor> partial, long bm) {
+         c10::optional<torch::Tensor> partial, long bm, bool frag) {
     // bm: rows per block, 0 = the launcher's choice; 16/32/64 force one
-    // kernel variant (tests)
+    // kernel variant (tests). frag: w1..w3 are fragment-major images
+    // (mlp3_pack_frag) declared with the same shapes
     CHECK_GPU(x0); CHECK_CONT(x0);
     TORCH_CHECK(x0.dtype() == torch::kBFloat16, "mlp3_fwd: x0 must be bf16");
     const c10::cuda::CUDAGuard guard(x0.device());
@@ -1118,6 +1165,9 @@ mlp3_fwd(torch::Tensor x0, torch::Tensor w1, torch::Tensor b1,
     TORCH_CHECK(bm == 0 || bm == 16 || ((bm == 32 || bm == 64)
                                         && K0p <= 416),
                 "mlp3_fwd: bm must be 0, 16, 32 or 64 (32/64: K0p <= 416)");
+    if (frag) {   // an image is one linear run of H x Kp elements
+        CHECK_CONT(w1); CHECK_CONT(w2); CHECK_CONT(w3);
+    }
     auto a1 = torch::empty({M, H}, x0.options());
     auto a2 = torch::empty({M, H}, x0.options());
     auto a3 = torch::empty({M, H}, x0.options());
@@ -1133,7 +1183,7 @@ mlp3_fwd(torch::Tensor x0, torch::Tensor w1, torch::Tensor b1,
                  w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
                  w3.data_ptr(), b3.data_ptr(), w4.data_ptr(), b4.data_ptr(),
                  pp, H, Hp, a1.data_ptr(), a2.data_ptr(), a3.data_ptr(),
-                 out.data_ptr<float>(), (int)bm, cur_stream());
+                 out.data_ptr<float>(), (int)bm, (int)frag, cur_stream());
     return {out, a1, a2, a3};
 }
 
@@ -1141,9 +1191,10 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 mlp3_bwd(torch::Tensor dout, torch::Tensor a1, torch::Tensor a2,
          torch::Tensor a3, torch::Tensor w4, torch::Tensor w3t,
          torch::Tensor w2t, torch::Tensor w1t, OptTensor bias_scratch,
-         long bm) {
+         long bm, bool frag) {
     // bias_scratch ([4H+1] fp32): when given, the dz3 assembly loop also
-    // accumulates dw4 (dout.a3 column sums) and db4 into segments 3H/4H
+    // accumulates dw4 (dout.a3 column sums) and db4 into segments 3H/4H.
+    // frag: w3t..w1t are fragment-major images (mlp3_pack_frag)
     CHECK_GPU(dout); CHECK_CONT(dout); CHECK_CONT(w3t); CHECK_CONT(w2t);
     CHECK_CONT(w1t);
     const c10::cuda::CUDAGuard guard(dout.device());
@@ -1170,7 +1221,7 @@ mlp3_bwd(torch::Tensor dout, torch::Tensor a1, torch::Tensor a2,
                  a2.data_ptr(), a3.data_ptr(), w4.data_ptr(), w3t.data_ptr(),
                  w2t.data_ptr(), w1t.data_ptr(), H, Hp, dz1.data_ptr(),
                  dz2.data_ptr(), dz3.data_ptr(), dx0.data_ptr(), bptr,
-                 (int)bm, cur_stream());
+                 (int)bm, (int)frag, cur_stream());
     return {dx0, dz1, dz2, dz3};
 }
 
@@ -1260,16 +1311,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("a3"), pybind11::arg("w4"), pybind11::arg("w3t"),
           pybind11::arg("w2t"), pybind11::arg("w1t"),
           pybind11::arg("bias_scratch") = pybind11::none(),
-          pybind11::arg("bm") = 0);
+          pybind11::arg("bm") = 0, pybind11::arg("frag") = false);
     m.def("mlp3_pack", &mlp3_pack,
           "refresh three padded (or transposed) weight copies in one "
           "launch");
+    m.def("mlp3_pack_frag", &mlp3_pack_frag,
+          "write up to six fragment-major weight images (pads included) "
+          "in one launch",
+          pybind11::arg("srcs"), pybind11::arg("dsts"),
+          pybind11::arg("trans"));
     m.def("mlp3_fwd", &mlp3_fwd,
           "fused 3-hidden-layer MLP forward (bf16 MFMA, bias+ReLU fused)",
           pybind11::arg("x0"), pybind11::arg("w1"), pybind11::arg("b1"),
           pybind11::arg("w2"), pybind11::arg("b2"), pybind11::arg("w3"),
           pybind11::arg("b3"), pybind11::arg("w4"), pybind11::arg("b4"),
-          pybind11::arg("partial"), pybind11::arg("bm") = 0);
+          pybind11::arg("partial"), pybind11::arg("bm") = 0,
+          pybind11::arg("frag") = false);
     m.def("mlp3_wgrad", &mlp3_wgrad,
           pybind11::arg("dz1"), pybind11::arg("dz2"), pybind11::arg("dz3"),
           pybind11::arg("x0"), pybind11::arg("a1"), pybind11::arg("a2"),

@@ -39,22 +39,41 @@ static __device__ __forceinline__ bf16x8 ld_frag(const mbf16* p) {
         __builtin_assume_aligned(p, 16));
 }
 
+// Weight layouts. The fragment map above fixes which lane holds which
+// (n, k), not where the element lives in memory, and the kernels take the
+// padded weights [N, Kp] in either of two images (template flag FRAG):
+//   row-major      lane's piece of k-step s of column chunk c at
+//                  (c + lane&15) * Kp + (lane>>4)*8 + 32*s: the 16 lanes of
+//                  a quarter-wave sit in 16 rows = 16 cache lines, a wave
+//                  load is 64 separate 16-byte L1 accesses;
+//   fragment-major element (n, k) at
+//                  ((n/16 * KS + k/32) * 64 + (k%32)/8 * 16 + n%16) * 8 + k%8
+//                  (KS = Kp/32), i.e. [N/16][KS][4][16][8]: lane l's piece of
+//                  k-step s of chunk c is the 16 bytes at
+//                  ((c/16 * KS + s) * 64 + l) * 8 — a wave load is one
+//                  contiguous 1 KB block (8 full lines), a chunk one KS KB
+//                  run. Written by k_mlp3_pack_frag.
+// Both start a chunk at c * Kp; they differ in the lane's offset inside it
+// and in the stride between k-steps. The (lane, element) <-> (n, k) map and
+// the k-order are the same, so every fp32 sum is too.
+#define MLP_BSTEP(frag) ((frag) ? 512 : 32)   // elements between k-steps
+
 // 16x16 tile over a padded contraction: A [.., lda] row-major, W [N, ldw]
-// row-major (B = W[n][k]); Kp % 32 == 0.
+// (B = W[n][k]; row-major or fragment-major, ldw = Kp); Kp % 32 == 0.
 //
 // M=16 per block means the W stream has NO reuse inside the block — the
 // "decode-GEMV" regime of the perf guide: load straight to VGPRs with a
 // DEEP UNROLL and late counted waits, so all K-steps' loads are in flight
 // before the first MFMA needs its operands (a 2-deep pipeline left ~200
 // cycles of L2 latency exposed per step: 80-90 us/kernel measured).
-template <int KS>
+template <int KS, int BST>
 static __device__ __forceinline__ f32x4 tile16_u(
         const mbf16* __restrict__ pa, const mbf16* __restrict__ pb) {
     bf16x8 a[KS], b[KS];
     #pragma unroll
     for (int s = 0; s < KS; ++s) {
         a[s] = ld_frag(pa + 32 * s);
-        b[s] = ld_frag(pb + 32 * s);
+        b[s] = ld_frag(pb + BST * s);
     }
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     #pragma unroll
@@ -64,21 +83,24 @@ static __device__ __forceinline__ f32x4 tile16_u(
     return acc;
 }
 
+template <bool FRAG>
 static __device__ __forceinline__ f32x4 tile16(
         const mbf16* Arow, const mbf16* W, long ldw, long n0,
         long Kp, int lane) {      // Arow: the lane's A row (m = lane&15)
+    constexpr int BST = MLP_BSTEP(FRAG);
     const long koff = (lane >> 4) * 8;
     const mbf16* pa = Arow + koff;
-    const mbf16* pb = W + (n0 + (lane & 15)) * ldw + koff;
-    if (Kp == 256) return tile16_u<8>(pa, pb);    // K0 = 247 padded
-    if (Kp == 416) return tile16_u<13>(pa, pb);   // H = 400 padded
-    if (Kp == 128) return tile16_u<4>(pa, pb);
+    const mbf16* pb = FRAG ? W + n0 * ldw + lane * 8
+                           : W + (n0 + (lane & 15)) * ldw + koff;
+    if (Kp == 256) return tile16_u<8, BST>(pa, pb);    // K0 = 247 padded
+    if (Kp == 416) return tile16_u<13, BST>(pa, pb);   // H = 400 padded
+    if (Kp == 128) return tile16_u<4, BST>(pa, pb);
     // generic fallback: 2-stage pipeline
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     bf16x8 a0 = ld_frag(pa), b0 = ld_frag(pb);
     for (long kb = 32; kb < Kp; kb += 32) {
         bf16x8 a1 = ld_frag(pa + kb);
-        bf16x8 b1 = ld_frag(pb + kb);
+        bf16x8 b1 = ld_frag(pb + kb * (BST / 32));
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc, 0, 0, 0);
         a0 = a1; b0 = b1;
     }
@@ -139,6 +161,21 @@ static __device__ __forceinline__ void mlp_load_mask(
     }
 }
 
+// fragment-major: the lane's piece of k-step 0 of column chunk c/16. c is
+// wave-uniform, which the compiler cannot see (it derives from
+// threadIdx.x >> 6). The 1 KB k-step stride leaves the load's immediate-
+// offset range after 4 steps, so a chunk needs a base per 4 k-steps where
+// the row-major form needs one; with readfirstlane the chunk part of them
+// is scalar arithmetic. Without it bwd<32> spilled 16 B/lane and the BM=64
+// kernels grew by 1-2 VGPRs; with it every instantiation is at or below
+// its row-major twin (docs/kernels.md).
+template <int KS>
+static __device__ __forceinline__ const mbf16* mlp_frag_chunk(
+        const mbf16* W, int c, int lane) {
+    return W + __builtin_amdgcn_readfirstlane(c) * (KS * 32)
+             + (unsigned)(lane * 8);
+}
+
 // one layer: lds_out/save <- relu(A @ W^T + b) (relu/bias optional) for
 // the block's RT row tiles and N output columns.
 //
@@ -163,7 +200,7 @@ static __device__ __forceinline__ void mlp_load_mask(
 // rot: the block's first column chunk is rotated by blockIdx.x, so that
 // concurrent blocks stream different weight rows instead of all walking
 // the same addresses in lockstep. Each output column sees the same k-order.
-template <int KS, int RT>
+template <int KS, int RT, bool FRAG>
 static __device__ __forceinline__ void mlp_layer_u(
         const mbf16* A, int lda, int a_rows, long m0, long M,
         const mbf16* W, int ldw, const mbf16* bias, int N,
@@ -171,6 +208,7 @@ static __device__ __forceinline__ void mlp_layer_u(
         mbf16* lds_out, mbf16* save, long save_ld,
         int wave, int lane, bool relu, bool sync_first) {
     constexpr int AR = RT <= 2 ? RT : 1;
+    constexpr int BST = MLP_BSTEP(FRAG);
     const int koff = (lane >> 4) * 8, col = lane & 15;
     const int nch = N >> 4;
     const int rot = (int)(blockIdx.x % (unsigned)nch);
@@ -185,9 +223,10 @@ static __device__ __forceinline__ void mlp_layer_u(
     if (c >= nch) c -= nch;
     c *= 16;
     if (li < nch) {
-        const mbf16* pb = W + (c + col) * ldw + koff;
+        const mbf16* pb = FRAG ? mlp_frag_chunk<KS>(W, c, lane)
+                               : W + (c + col) * ldw + koff;
         #pragma unroll
-        for (int s = 0; s < KS; ++s) b0[s] = ld_frag(pb + 32 * s);
+        for (int s = 0; s < KS; ++s) b0[s] = ld_frag(pb + BST * s);
     }
     if (sync_first) __syncthreads();
 
@@ -210,9 +249,10 @@ static __device__ __forceinline__ void mlp_layer_u(
         if (cn >= nch) cn -= nch;
         cn *= 16;
         if (li + MLP_WAVES < nch) {
-            const mbf16* pb = W + (cn + col) * ldw + koff;
+            const mbf16* pb = FRAG ? mlp_frag_chunk<KS>(W, cn, lane)
+                                   : W + (cn + col) * ldw + koff;
             #pragma unroll
-            for (int s = 0; s < KS; ++s) b1[s] = ld_frag(pb + 32 * s);
+            for (int s = 0; s < KS; ++s) b1[s] = ld_frag(pb + BST * s);
         }
         #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
@@ -241,7 +281,7 @@ static __device__ __forceinline__ void mlp_layer_u(
     }
 }
 
-template <int RT>
+template <int RT, bool FRAG>
 static __device__ __forceinline__ void mlp_layer(
         const mbf16* A, int lda, int a_rows, long m0, long M,
         const mbf16* W, int ldw, const mbf16* bias, int N, int Kp,
@@ -249,13 +289,15 @@ static __device__ __forceinline__ void mlp_layer(
         mbf16* lds_out, mbf16* save, long save_ld,
         int wave, int lane, bool relu, bool sync_first) {
     if (Kp == 256)
-        return mlp_layer_u<8, RT>(A, lda, a_rows, m0, M, W, ldw, bias, N, mask_act,
-                                  mask_ld, lds_out, save, save_ld, wave,
-                                  lane, relu, sync_first);
+        return mlp_layer_u<8, RT, FRAG>(A, lda, a_rows, m0, M, W, ldw, bias,
+                                        N, mask_act, mask_ld, lds_out, save,
+                                        save_ld, wave, lane, relu,
+                                        sync_first);
     if (Kp == 416)
-        return mlp_layer_u<13, RT>(A, lda, a_rows, m0, M, W, ldw, bias, N, mask_act,
-                                   mask_ld, lds_out, save, save_ld, wave,
-                                   lane, relu, sync_first);
+        return mlp_layer_u<13, RT, FRAG>(A, lda, a_rows, m0, M, W, ldw, bias,
+                                         N, mask_act, mask_ld, lds_out, save,
+                                         save_ld, wave, lane, relu,
+                                         sync_first);
     // generic (unpipelined) fallback for other shapes
     if (sync_first) __syncthreads();
     const bool masked = mask_act != nullptr;
@@ -266,7 +308,7 @@ static __device__ __forceinline__ void mlp_layer(
         #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
             const int ar = min(rt * 16 + (lane & 15), a_rows - 1);
-            f32x4 acc = tile16(A + ar * lda, W, ldw, c, Kp, lane);
+            f32x4 acc = tile16<FRAG>(A + ar * lda, W, ldw, c, Kp, lane);
             mlp_epilogue(acc, bv, relu, masked, mk[rt], rt, m0, M, c, lane,
                          lds_out, save, save_ld);
         }
@@ -283,10 +325,12 @@ static __device__ __forceinline__ void mlp_zero_lds(mbf16* p, int n16) {
         z[i] = u32x4{0u, 0u, 0u, 0u};
 }
 
-template <int BM>
+template <int BM, bool FRAG>
 __global__ __launch_bounds__(64 * MLP_WAVES, 2)
 void k_mlp3_fwd(const mbf16* __restrict__ x0, long M, long K0p,
-                const mbf16* __restrict__ w1,   // [H, K0p] padded
+                const mbf16* __restrict__ w1,   // [H, K0p] padded; the
+                                                // weights row-major or
+                                                // fragment-major (FRAG)
                 const mbf16* __restrict__ b1,
                 const mbf16* __restrict__ w2,   // [H, Hp] padded
                 const mbf16* __restrict__ b2,
@@ -329,12 +373,15 @@ void k_mlp3_fwd(const mbf16* __restrict__ x0, long M, long K0p,
         lda1 = MLP_LD;
         a_rows1 = BM;
     }
-    mlp_layer<RT>(A1, lda1, a_rows1, m0, M, w1, (int)K0p, b1, (int)H, (int)K0p,
-                  nullptr, 0, act0, a1, H, wave, lane, true, true);
-    mlp_layer<RT>(act0, MLP_LD, BM, m0, M, w2, (int)Hp, b2, (int)H, (int)Hp,
-                  nullptr, 0, act1, a2, H, wave, lane, true, true);
-    mlp_layer<RT>(act1, MLP_LD, BM, m0, M, w3, (int)Hp, b3, (int)H, (int)Hp,
-                  nullptr, 0, act0, a3, H, wave, lane, true, true);
+    mlp_layer<RT, FRAG>(A1, lda1, a_rows1, m0, M, w1, (int)K0p, b1, (int)H,
+                        (int)K0p, nullptr, 0, act0, a1, H, wave, lane, true,
+                        true);
+    mlp_layer<RT, FRAG>(act0, MLP_LD, BM, m0, M, w2, (int)Hp, b2, (int)H,
+                        (int)Hp, nullptr, 0, act1, a2, H, wave, lane, true,
+                        true);
+    mlp_layer<RT, FRAG>(act1, MLP_LD, BM, m0, M, w3, (int)Hp, b3, (int)H,
+                        (int)Hp, nullptr, 0, act0, a3, H, wave, lane, true,
+                        true);
     __syncthreads();
 
     // final Linear(H, 1): VALU dot per row
@@ -354,7 +401,7 @@ void k_mlp3_fwd(const mbf16* __restrict__ x0, long M, long K0p,
     }
 }
 
-template <int BM>
+template <int BM, bool FRAG>
 __global__ __launch_bounds__(64 * MLP_WAVES, 2)
 void k_mlp3_bwd(const float* __restrict__ dout, long M, long K0p,
                 const mbf16* __restrict__ a1, const mbf16* __restrict__ a2,
@@ -419,13 +466,13 @@ void k_mlp3_bwd(const float* __restrict__ dout, long M, long K0p,
     // NOTE: dz tiles' pad columns [H, Hp) may hold garbage after a GEMM
     // stage — harmless, because the B side (padded weight copies) is zero
     // there, so pad products vanish.
-    mlp_layer<RT>(dzA, MLP_LD, BM, m0, M, w3t, (int)Hp, nullptr, Hi, (int)Hp,
-                  a2, H, dzB, dz2, H, wave, lane, false, true);
-    mlp_layer<RT>(dzB, MLP_LD, BM, m0, M, w2t, (int)Hp, nullptr, Hi, (int)Hp,
-                  a1, H, dzA, dz1, H, wave, lane, false, true);
-    mlp_layer<RT>(dzA, MLP_LD, BM, m0, M, w1t, (int)Hp, nullptr, (int)K0p,
-                  (int)Hp, nullptr, 0, nullptr, dx0, K0p, wave, lane, false,
-                  true);
+    mlp_layer<RT, FRAG>(dzA, MLP_LD, BM, m0, M, w3t, (int)Hp, nullptr, Hi,
+                        (int)Hp, a2, H, dzB, dz2, H, wave, lane, false, true);
+    mlp_layer<RT, FRAG>(dzB, MLP_LD, BM, m0, M, w2t, (int)Hp, nullptr, Hi,
+                        (int)Hp, a1, H, dzA, dz1, H, wave, lane, false, true);
+    mlp_layer<RT, FRAG>(dzA, MLP_LD, BM, m0, M, w1t, (int)Hp, nullptr,
+                        (int)K0p, (int)Hp, nullptr, 0, nullptr, dx0, K0p,
+                        wave, lane, false, true);
 }
 
 // Bias grads for all 3 hidden layers + the head scalar in one pass over
@@ -537,7 +584,23 @@ extern "C" void emb_mlp3_bias_bwd(const float* dout, const void* dz1,
 // Up to 16 rows x 256 CUs = 4096 rows BM=16 is fastest and keeps the most
 // blocks for small M; past it a second wave of blocks doubles its time
 // and the larger tile wins. t[] below are the one-wave times at M=4096.
-static int mlp_pick_bm(long M, long K0p, int bm, bool bwd) {
+//
+// The table above is the ROW-MAJOR weight layout (frag = false), where the
+// block time is the L1 access rate of the 16-byte fragment pieces. With the
+// fragment-major images (frag = true; same method: back-to-back launches,
+// best of 3 x 300, device events) the stream costs a quarter of the L1
+// accesses and every cell falls, BM=16 the most:
+//   M      BM=16          BM=32          BM=64
+//   1024   15.1 / 20.1    19.4 / 30.2    34.4 / 55.4
+//   2048   15.3 / 21.8    19.6 / 30.9    34.8 / 55.7
+//   4096   16.1 / 26.0    20.2 / 35.3    35.2 / 58.8
+//   8192   29.8 / 49.9    21.5 / 39.9    36.4 / 65.5
+// (row-major re-measured in the same run: within 0.3 us of the table
+// above, bwd BM=64 within 1.0). "BM = 16 while M/16 <= CUs" still holds,
+// by a wider margin (4096: 16.1 vs 20.2, 26.0 vs 35.3), and BM=32 still
+// wins past it (8192: 21.5 vs 29.8, 39.9 vs 49.9): the rule is unchanged,
+// the two layouts keep their own t[].
+static int mlp_pick_bm(long M, long K0p, int bm, bool bwd, bool frag) {
     if (K0p > MLP_LD - 8) return 16;
     if (bm == 16 || bm == 32 || bm == 64) return bm;
     static int cus = 0;
@@ -551,7 +614,10 @@ static int mlp_pick_bm(long M, long K0p, int bm, bool bwd) {
     }
     static const float t_fwd[3] = {25.3f, 28.2f, 40.8f};
     static const float t_bwd[3] = {32.2f, 39.1f, 61.8f};
-    const float* t = bwd ? t_bwd : t_fwd;
+    static const float t_fwd_frag[3] = {16.1f, 20.2f, 35.2f};
+    static const float t_bwd_frag[3] = {26.0f, 35.3f, 58.8f};
+    const float* t = frag ? (bwd ? t_bwd_frag : t_fwd_frag)
+                          : (bwd ? t_bwd : t_fwd);
     int best = 16;
     float best_cost = 0.f;
     for (int i = 0; i < 3; ++i) {
@@ -572,7 +638,7 @@ static void mlp_allow_lds(K kernel, size_t bytes) {
                                   (int)bytes);
 }
 
-template <int BM>
+template <int BM, bool FRAG>
 static void mlp_launch_fwd(const void* x0, long M, long K0p,
                            const void* w1, const void* b1,
                            const void* w2, const void* b2,
@@ -582,9 +648,9 @@ static void mlp_launch_fwd(const void* x0, long M, long K0p,
                            void* a1, void* a2, void* a3, float* out,
                            hipStream_t stream) {
     const size_t lds = 2 * BM * MLP_LD * sizeof(mbf16);
-    mlp_allow_lds(&k_mlp3_fwd<BM>, lds);
+    mlp_allow_lds(&k_mlp3_fwd<BM, FRAG>, lds);
     const long grid = (M + BM - 1) / BM;
-    k_mlp3_fwd<BM><<<(int)grid, 64 * MLP_WAVES, lds, stream>>>(
+    k_mlp3_fwd<BM, FRAG><<<(int)grid, 64 * MLP_WAVES, lds, stream>>>(
         (const mbf16*)x0, M, K0p, (const mbf16*)w1, (const mbf16*)b1,
         (const mbf16*)w2, (const mbf16*)b2, (const mbf16*)w3,
         (const mbf16*)b3, (const mbf16*)w4, (const mbf16*)b4, partial, H, Hp,
@@ -599,16 +665,20 @@ extern "C" void emb_mlp3_fwd(const void* x0, long M, long K0p,
                              const float* partial,
                              long H, long Hp,
                              void* a1, void* a2, void* a3, float* out,
-                             int bm, hipStream_t stream) {
+                             int bm, int frag, hipStream_t stream) {
     if (M == 0) return;
-    bm = mlp_pick_bm(M, K0p, bm, false);
-    auto fn = bm == 64 ? mlp_launch_fwd<64>
-            : bm == 32 ? mlp_launch_fwd<32> : mlp_launch_fwd<16>;
+    bm = mlp_pick_bm(M, K0p, bm, false, frag != 0);
+    auto fn = frag ? (bm == 64 ? mlp_launch_fwd<64, true>
+                      : bm == 32 ? mlp_launch_fwd<32, true>
+                                 : mlp_launch_fwd<16, true>)
+                   : (bm == 64 ? mlp_launch_fwd<64, false>
+                      : bm == 32 ? mlp_launch_fwd<32, false>
+                                 : mlp_launch_fwd<16, false>);
     fn(x0, M, K0p, w1, b1, w2, b2, w3, b3, w4, b4, partial, H, Hp, a1, a2,
        a3, out, stream);
 }
 
-template <int BM>
+template <int BM, bool FRAG>
 static void mlp_launch_bwd(const float* dout, long M, long K0p,
                            const void* a1, const void* a2, const void* a3,
                            const void* w4, const void* w3t,
@@ -617,9 +687,9 @@ static void mlp_launch_bwd(const float* dout, long M, long K0p,
                            void* dz1, void* dz2, void* dz3, void* dx0,
                            float* bias_out, hipStream_t stream) {
     const size_t lds = 2 * BM * MLP_LD * sizeof(mbf16);
-    mlp_allow_lds(&k_mlp3_bwd<BM>, lds);
+    mlp_allow_lds(&k_mlp3_bwd<BM, FRAG>, lds);
     const long grid = (M + BM - 1) / BM;
-    k_mlp3_bwd<BM><<<(int)grid, 64 * MLP_WAVES, lds, stream>>>(
+    k_mlp3_bwd<BM, FRAG><<<(int)grid, 64 * MLP_WAVES, lds, stream>>>(
         dout, M, K0p, (const mbf16*)a1, (const mbf16*)a2, (const mbf16*)a3,
         (const mbf16*)w4, (const mbf16*)w3t, (const mbf16*)w2t,
         (const mbf16*)w1t, H, Hp, (mbf16*)dz1, (mbf16*)dz2, (mbf16*)dz3,
@@ -632,12 +702,17 @@ extern "C" void emb_mlp3_bwd(const float* dout, long M, long K0p,
                              const void* w2t, const void* w1t,
                              long H, long Hp,
                              void* dz1, void* dz2, void* dz3, void* dx0,
-                             float* bias_out, int bm, hipStream_t stream) {
+                             float* bias_out, int bm, int frag,
+                             hipStream_t stream) {
     if (M == 0) return;
     // the backward has no x0 tile in LDS: any K0p works with every BM
-    bm = mlp_pick_bm(M, 0, bm, true);
-    auto fn = bm == 64 ? mlp_launch_bwd<64>
-            : bm == 32 ? mlp_launch_bwd<32> : mlp_launch_bwd<16>;
+    bm = mlp_pick_bm(M, 0, bm, true, frag != 0);
+    auto fn = frag ? (bm == 64 ? mlp_launch_bwd<64, true>
+                      : bm == 32 ? mlp_launch_bwd<32, true>
+                                 : mlp_launch_bwd<16, true>)
+                   : (bm == 64 ? mlp_launch_bwd<64, false>
+                      : bm == 32 ? mlp_launch_bwd<32, false>
+                                 : mlp_launch_bwd<16, false>);
     fn(dout, M, K0p, a1, a2, a3, w4, w3t, w2t, w1t, H, Hp, dz1, dz2, dz3,
        dx0, bias_out, stream);
 }
@@ -967,4 +1042,90 @@ extern "C" void emb_mlp3_pack(const void* w1, void* d1, long r1, long c1,
     if (threads > 256) threads = 256;
     dim3 grid((unsigned)mx, 3);
     k_mlp3_pack<<<grid, threads, 0, stream>>>(p0, p1, p2);
+}
+
+// ---- fragment-major weight images -------------------------------------
+// One launch writes up to six fragment-major images (layout: top of this
+// file): the train step's w1, w2, w3 and the dgrad operands w3^T, w2^T,
+// w1^T. gridDim.y selects the matrix, blockIdx.x a 16-column chunk of it,
+// and the block's threads walk the chunk's KS x 64 16-byte pieces in
+// destination order — thread t writes piece t of a contiguous KS KB run,
+// s = t >> 6 and lane = t & 63 are shifts, all indices 32-bit.
+//
+// The WHOLE destination is written: a piece is assembled in registers and
+// every (n, k) outside the source's valid region becomes zero, so the pads
+// do not depend on how the buffer was allocated (0 x garbage = NaN).
+// Source reads are 2-byte (w1 has 247 columns: its rows are not 16-byte
+// aligned) except where a plain source's piece is aligned and entirely
+// inside the row; transposed sources read 16 consecutive n per quarter-
+// wave and element. Both ride L2 (the matrices are 100s of KB).
+
+struct PackFragOne {
+    const mbf16* src;   // [rows, src_ld] row-major, valid [rows, cols]
+    mbf16* dst;         // fragment-major image of [N, Kp]
+    int rows, cols, src_ld, nch, ks, trans;   // nch = N/16, ks = Kp/32
+};
+
+extern "C" __global__ void k_mlp3_pack_frag(
+        PackFragOne p0, PackFragOne p1, PackFragOne p2,
+        PackFragOne p3, PackFragOne p4, PackFragOne p5) {
+    const int y = (int)blockIdx.y;
+    PackFragOne p = y == 0 ? p0 : y == 1 ? p1 : y == 2 ? p2
+                  : y == 3 ? p3 : y == 4 ? p4 : p5;
+    const int ch = (int)blockIdx.x;
+    if (ch >= p.nch) return;
+    const unsigned short* src =
+        reinterpret_cast<const unsigned short*>(p.src);
+    u32x4* dst = reinterpret_cast<u32x4*>(p.dst) + ch * p.ks * 64;
+    // the image is of W' = src (plain) or src^T (trans): W'[n][k]
+    const int nmax = p.trans ? p.cols : p.rows;
+    const int kmax = p.trans ? p.rows : p.cols;
+    const bool vec = !p.trans && (p.src_ld & 7) == 0
+                  && (reinterpret_cast<uintptr_t>(p.src) & 15) == 0;
+    for (int t = (int)threadIdx.x; t < p.ks * 64; t += (int)blockDim.x) {
+        const int lane = t & 63;
+        const int n = ch * 16 + (lane & 15);
+        const int k = (t >> 6) * 32 + (lane >> 4) * 8;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (n < nmax && k < kmax) {
+            if (vec && k + 8 <= kmax) {
+                v = *reinterpret_cast<const u32x4*>(
+                    __builtin_assume_aligned(src + n * p.src_ld + k, 16));
+            } else {
+                const unsigned short* sp =
+                    p.trans ? src + k * p.src_ld + n : src + n * p.src_ld + k;
+                const int step = p.trans ? p.src_ld : 1;
+                unsigned e[8];
+                #pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    e[i] = k + i < kmax ? (unsigned)sp[i * step] : 0u;
+                v = u32x4{e[0] | e[1] << 16, e[2] | e[3] << 16,
+                          e[4] | e[5] << 16, e[6] | e[7] << 16};
+            }
+        }
+        dst[t] = v;
+    }
+}
+
+// n <= 6 matrices; rows/cols/src_ld describe the source, N/Kp the image
+extern "C" void emb_mlp3_pack_frag(int n, const void* const* srcs,
+                                   void* const* dsts, const long* rows,
+                                   const long* cols, const long* src_ld,
+                                   const long* N, const long* Kp,
+                                   const int* trans, hipStream_t stream) {
+    PackFragOne p[6] = {};
+    int mx = 0, mk = 0;
+    for (int i = 0; i < n && i < 6; ++i) {
+        p[i] = PackFragOne{(const mbf16*)srcs[i], (mbf16*)dsts[i],
+                           (int)rows[i], (int)cols[i], (int)src_ld[i],
+                           (int)(N[i] / 16), (int)(Kp[i] / 32), trans[i]};
+        if (p[i].nch > mx) mx = p[i].nch;
+        if (p[i].ks > mk) mk = p[i].ks;
+    }
+    if (!mx || !mk) return;
+    // one thread per piece of the longest chunk, at most 1024
+    int threads = mk * 64 > 1024 ? 1024 : mk * 64;
+    dim3 grid((unsigned)mx, (unsigned)n);
+    k_mlp3_pack_frag<<<grid, threads, 0, stream>>>(p[0], p[1], p[2], p[3],
+                                                   p[4], p[5]);
 }
