@@ -26,6 +26,15 @@ typedef struct ihipStream_t* hipStream_t_;
 extern "C" {
 void emb_unique(const i64*, long, u64*, int*, long, int*, unsigned char*,
                 i64*, i64*, int*, const i64*, int, hipStream_t_);
+void emb_unique_indexed(const i64*, long, u64*, int*, long, int*,
+                        unsigned char*, i64*, i64*, int*, const i64*, int,
+                        int*, int*, int*, int*, int*, int*, int*, long, int*,
+                        int*, hipStream_t_);
+int emb_seg_threshold();
+int emb_seg_max_dim();
+void emb_reduce_by_index(const int*, const int*, const int*, const int*,
+                         const int*, long, const float*, long, long,
+                         const int*, float*, u64*, hipStream_t_);
 void emb_ht_lookup(u64*, int*, long, const i64*, long, int*, i64*, i64*,
                    unsigned char*, int, const int*, long, hipStream_t_);
 void emb_ht_rehash(const u64*, const int*, long, u64*, int*, long,
@@ -150,8 +159,11 @@ const int* u_ptr(const OptTensor& u_dev) {
 
 // ---- unique ----------------------------------------------------------
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> unique_bounded(
-    torch::Tensor keys, OptTensor field_offsets) {
+// shared body of unique_bounded / unique_bounded_indexed: {uk, inverse,
+// counter} and, when ``indexed``, {seg_off, seg_cnt, perm, long_list,
+// n_long} behind them
+std::vector<torch::Tensor> unique_bounded_impl(
+    torch::Tensor keys, OptTensor field_offsets, bool indexed) {
     CHECK_GPU(keys); CHECK_CONT(keys);
     TORCH_CHECK(keys.dtype() == torch::kInt64);
     const i64* foff = nullptr;
@@ -178,12 +190,53 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> unique_bounded(
     auto uk = torch::empty({n}, opts_i64);  // tail unread
     auto inverse = torch::empty({n}, opts_i64);
     auto counter = torch::empty({1}, opts_i32);
-    emb_unique(keys.data_ptr<i64>(), n, (u64*)tk.data_ptr<i64>(),
-               tv.data_ptr<int>(), cap, slot_of.data_ptr<int>(),
-               is_first.data_ptr<uint8_t>(), uk.data_ptr<i64>(),
-               inverse.data_ptr<i64>(), counter.data_ptr<int>(), foff, F,
-               cur_stream());
-    return {uk, inverse, counter};
+    if (!indexed) {
+        emb_unique(keys.data_ptr<i64>(), n, (u64*)tk.data_ptr<i64>(),
+                   tv.data_ptr<int>(), cap, slot_of.data_ptr<int>(),
+                   is_first.data_ptr<uint8_t>(), uk.data_ptr<i64>(),
+                   inverse.data_ptr<i64>(), counter.data_ptr<int>(), foff, F,
+                   cur_stream());
+        return {uk, inverse, counter};
+    }
+    TORCH_CHECK(n < (1L << 31), "unique_bounded_indexed: n must fit int32");
+    // tcount | toff share one allocation, seg_off | seg_cnt | perm | rank
+    // another; the two bump counters sit 64 bytes apart
+    auto tct = torch::empty({2, cap}, opts_i32);
+    auto segs = torch::empty({4, n}, opts_i32);
+    long long_cap = n / (emb_seg_threshold() + 1) + 1;
+    auto long_list = torch::empty({long_cap}, opts_i32);
+    auto ctr = torch::empty({32}, opts_i32);
+    auto seg_off = segs.select(0, 0), seg_cnt = segs.select(0, 1);
+    auto perm = segs.select(0, 2), rank = segs.select(0, 3);
+    auto n_long = ctr.narrow(0, 16, 1);
+    emb_unique_indexed(keys.data_ptr<i64>(), n, (u64*)tk.data_ptr<i64>(),
+                       tv.data_ptr<int>(), cap, slot_of.data_ptr<int>(),
+                       is_first.data_ptr<uint8_t>(), uk.data_ptr<i64>(),
+                       inverse.data_ptr<i64>(), counter.data_ptr<int>(), foff,
+                       F, tct.data_ptr<int>(), tct.data_ptr<int>() + cap,
+                       rank.data_ptr<int>(), seg_off.data_ptr<int>(),
+                       seg_cnt.data_ptr<int>(), perm.data_ptr<int>(),
+                       long_list.data_ptr<int>(), long_cap,
+                       ctr.data_ptr<int>(), n_long.data_ptr<int>(),
+                       cur_stream());
+    return {uk, inverse, counter, seg_off, seg_cnt, perm, long_list, n_long};
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> unique_bounded(
+    torch::Tensor keys, OptTensor field_offsets) {
+    auto r = unique_bounded_impl(keys, field_offsets, false);
+    return {r[0], r[1], r[2]};
+}
+
+// unique_bounded plus the inverted index of the batch (embops.hip,
+// "segmented reduce"): uid's elements are perm[seg_off[uid] ..
+// seg_off[uid] + seg_cnt[uid]); long_list[:n_long] names the uids with more
+// than seg_reduce_threshold() elements. All int32, device-resident.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+unique_bounded_indexed(torch::Tensor keys, OptTensor field_offsets) {
+    auto r = unique_bounded_impl(keys, field_offsets, true);
+    return {r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]};
 }
 
 std::tuple<torch::Tensor, torch::Tensor> unique_inverse(torch::Tensor keys) {
@@ -291,6 +344,42 @@ std::tuple<torch::Tensor, torch::Tensor> reduce_by_inverse(
     emb_reduce_by_inverse(inverse.data_ptr<i64>(), grads.data_ptr<float>(), n,
                           dim, ugrads.data_ptr<float>(),
                           (u64*)counts.data_ptr<i64>(), u, cur_stream());
+    return {ugrads, counts};
+}
+
+// Same (ugrads [n, dim], counts [n]) as reduce_by_inverse(inverse, grads, n),
+// summed through the inverted index of unique_bounded_indexed: no atomics,
+// and rows at and beyond *u_dev come back as zeros with count 0.
+std::tuple<torch::Tensor, torch::Tensor> reduce_by_index(
+    torch::Tensor seg_off, torch::Tensor seg_cnt, torch::Tensor perm,
+    torch::Tensor long_list, torch::Tensor n_long, torch::Tensor grads,
+    torch::Tensor u_dev) {
+    CHECK_GPU(grads); CHECK_CONT(grads);
+    TORCH_CHECK(grads.dtype() == torch::kFloat32 && grads.dim() == 2,
+                "reduce_by_index: grads must be float32 [n, dim]");
+    long n = grads.size(0);
+    long dim = grads.size(1);
+    TORCH_CHECK(dim <= emb_seg_max_dim(),
+                "reduce_by_index: dim above the kernel's ladder");
+    for (const auto* t : {&seg_off, &seg_cnt, &perm, &long_list, &n_long,
+                          &u_dev}) {
+        CHECK_GPU(*t); CHECK_CONT(*t);
+        TORCH_CHECK(t->dtype() == torch::kInt32,
+                    "reduce_by_index: index tensors must be int32");
+    }
+    TORCH_CHECK(seg_off.numel() == n && seg_cnt.numel() == n
+                && perm.numel() == n,
+                "reduce_by_index: index does not match grads");
+    TORCH_CHECK(n_long.numel() == 1 && u_dev.numel() == 1);
+    const c10::cuda::CUDAGuard guard(grads.device());
+    auto ugrads = torch::empty({n, dim}, grads.options());
+    auto counts = torch::empty({n}, grads.options().dtype(torch::kInt64));
+    emb_reduce_by_index(seg_off.data_ptr<int>(), seg_cnt.data_ptr<int>(),
+                        perm.data_ptr<int>(), long_list.data_ptr<int>(),
+                        n_long.data_ptr<int>(), long_list.numel(),
+                        grads.data_ptr<float>(), n, dim,
+                        u_dev.data_ptr<int>(), ugrads.data_ptr<float>(),
+                        (u64*)counts.data_ptr<i64>(), cur_stream());
     return {ugrads, counts};
 }
 
@@ -1242,6 +1331,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "row gather with fused lazy init (+ optional duplicate scatter)");
     m.def("reduce_by_inverse", &reduce_by_inverse,
           "grad reduce-by-key with counts (LDS-aggregated)");
+    m.def("unique_bounded_indexed", &unique_bounded_indexed,
+          "unique_bounded plus the batch's inverted index (seg_off, "
+          "seg_cnt, perm, long_list, n_long)",
+          pybind11::arg("keys"),
+          pybind11::arg("field_offsets") = pybind11::none());
+    m.def("reduce_by_index", &reduce_by_index,
+          "grad reduce-by-key with counts through the inverted index "
+          "(segmented, no atomics)");
+    m.def("seg_reduce_threshold", &emb_seg_threshold,
+          "list length above which a uid is in long_list");
+    m.def("seg_reduce_max_dim", &emb_seg_max_dim,
+          "widest dim reduce_by_index covers");
     m.def("pool_fwd", &pool_fwd,
           "segment-pooled gather (sum/mean/sqrtn) over ragged bags; also "
           "emits each element's bag for the backward",

@@ -68,13 +68,36 @@ static inline void fill_f32(float* p, long n, float v, hipStream_t s) {
 // One launch resetting all of emb_unique's scratch (table + counter +
 // is_first) — three separate fills cost ~2 extra kernel ramps per pull in
 // the captured train step.
+//
+// IDX = true is the indexed dedup (see "inverted index" below); UIdx holds
+// its scratch and outputs and is all-null for IDX = false.
+struct UIdx {
+    int* tcount;       // [cap] occurrences of the key in table slot s
+    int* toff;         // [cap] start of that key's list in perm
+    int* rank;         // [n] position of element i inside its key's list
+    int* seg_off;      // [n] per uid: list start in perm
+    int* seg_cnt;      // [n] per uid: list length
+    int* perm;         // [n] element ids grouped by uid
+    int* long_list;    // [long_cap] uids with seg_cnt > SEG_T
+    int* off_counter;  // bump allocator of perm ranges
+    int* n_long;       // live entries of long_list
+    long long_cap;
+};
+
+template <bool IDX>
 __global__ void k_unique_reset(u64* __restrict__ tk, long cap,
                                unsigned char* __restrict__ is_first, long n,
-                               int* __restrict__ counter) {
+                               int* __restrict__ counter, UIdx ix) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cap) tk[i] = ~0ull;   // EMPTY
+    if (i < cap) {
+        tk[i] = ~0ull;   // EMPTY
+        if constexpr (IDX) ix.tcount[i] = 0;
+    }
     if (i < n) is_first[i] = 0;
-    if (i == 0) *counter = 0;
+    if (i == 0) {
+        *counter = 0;
+        if constexpr (IDX) { *ix.off_counter = 0; *ix.n_long = 0; }
+    }
 }
 
 // Same idea for the reduce-by-key scratch (payload accumulator + counts).
@@ -159,18 +182,33 @@ DEV float init_value(int cat, float p0, float p1, float p2,
 #define ULDS 1024  // LDS pre-filter entries (8 KiB keys + 4 KiB slots)
 #define UA_ITERS 8  // elements per thread in the uid-assign kernel
 #define UI_ILP 4    // parallel lookups per thread in the inverse kernel
+#define SEG_T 32    // inverted index: lists longer than this are "long"
 
 // foff/F: optional per-field key offsets fused into the read (keys is then
 // the RAW [B, F] field-id layout; flat key = keys[i] + foff[i % F]) — saves
 // the broadcast-add launch + 8B/elem intermediate every pull.
+//
+// IDX: every element also learns its rank inside its key's list. The
+// block's copies of a key rank themselves with a returning LDS add on the
+// key's LDS entry; after the barrier the block winner reserves the block's
+// range with ONE returning global add on tcount[slot] and publishes the
+// base through LDS, so a hot key costs one global atomic per block, like
+// its CAS. Elements on the LDS-overflow route add 1 to tcount themselves.
+template <bool IDX>
 __global__ void k_unique_insert(const i64* __restrict__ keys, long n,
                                 u64* __restrict__ tk, long mask,
                                 int* __restrict__ slot_of,
                                 unsigned char* __restrict__ is_first,
-                                const i64* __restrict__ foff, int F) {
+                                const i64* __restrict__ foff, int F,
+                                UIdx ix) {
     __shared__ u64 lkeys[ULDS];
     __shared__ int lslot[ULDS];
-    for (int t = threadIdx.x; t < ULDS; t += blockDim.x) lkeys[t] = EMPTY;
+    __shared__ int lcnt[IDX ? ULDS : 1];    // block's copies of the key
+    __shared__ int lbase[IDX ? ULDS : 1];   // their base in the key's list
+    for (int t = threadIdx.x; t < ULDS; t += blockDim.x) {
+        lkeys[t] = EMPTY;
+        if constexpr (IDX) lcnt[t] = 0;
+    }
     __syncthreads();
 
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -181,6 +219,7 @@ __global__ void k_unique_insert(const i64* __restrict__ keys, long n,
         if (foff) kin += foff[(int)i % F];   // n < 2^31: 32-bit mod
     }
     int lh = -1;           // LDS slot of this element's key
+    int lr = 0;            // IDX: rank among the block's copies / own rank
     bool lds_winner = false, lds_ok = false;
     if (i < n && (u64)kin == EMPTY) {
         // RESERVED key -1 (the scratch table's empty marker, same value the
@@ -199,6 +238,8 @@ __global__ void k_unique_insert(const i64* __restrict__ keys, long n,
             if (cur == k) { lds_ok = true; break; }
             lh = (lh + 1) & (ULDS - 1);
         }
+        if constexpr (IDX)
+            if (lds_ok) lr = atomicAdd(&lcnt[lh], 1);
         if (lds_winner || !lds_ok) {
             // block winner (or LDS overflow): probe the global table.
             // Probes are BOUNDED by the table size: an overfull table (can
@@ -224,12 +265,35 @@ __global__ void k_unique_insert(const i64* __restrict__ keys, long n,
             slot_of[i] = found >= 0 ? (int)found : -1;
             if (lds_winner)
                 lslot[lh] = found >= 0 ? (int)found : (int)(-2 - i);
+            if constexpr (IDX)
+                if (!lds_ok && found >= 0)
+                    lr = atomicAdd(&ix.tcount[found], 1);
         }
     }
     __syncthreads();
     if (i < n && lds_ok && !lds_winner) slot_of[i] = lslot[lh];
+    if constexpr (IDX) {
+        if (lds_winner) {
+            // a winner without a table slot (global overflow) is a list of
+            // one; its block duplicates are then in no list (file header
+            // of the inverted index: wrong numbers, never a bad access)
+            int s = lslot[lh];
+            lbase[lh] = s >= 0 ? atomicAdd(&ix.tcount[s], lcnt[lh]) : 0;
+        }
+        __syncthreads();
+        if (i < n) ix.rank[i] = lds_ok ? lbase[lh] + lr : lr;
+    }
 }
 
+//
+// IDX: a first occurrence also reads its key's final count tcount[slot]
+// and takes the key's range of perm from a second bump counter: the
+// thread's counts are summed, a wave scan turns them into offsets and lane
+// 0 reserves the wave's total beside the uid range, so the kernel still
+// waits on one round of returning atomics per wave. Offsets therefore do
+// not follow uid order. A first occurrence without a slot (reserved -1,
+// global overflow) is a list of one and files itself in perm here.
+template <bool IDX>
 __global__ void k_unique_assign(const i64* __restrict__ keys, long n,
                                 const int* __restrict__ slot_of,
                                 const unsigned char* __restrict__ is_first,
@@ -237,7 +301,8 @@ __global__ void k_unique_assign(const i64* __restrict__ keys, long n,
                                 i64* __restrict__ unique_keys,
                                 int* __restrict__ counter,
                                 i64* __restrict__ inverse,
-                                const i64* __restrict__ foff, int F) {
+                                const i64* __restrict__ foff, int F,
+                                UIdx ix) {
     // UA_ITERS elements per thread with ONE returning atomic per wave:
     // ballots for all iterations are taken first (independent loads in
     // flight), their popcounts summed, a single atomicAdd reserves the uid
@@ -248,18 +313,44 @@ __global__ void k_unique_assign(const i64* __restrict__ keys, long n,
     const long stride = (long)gridDim.x * blockDim.x;
     long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
     u64 ballots[UA_ITERS];
+    int sl[IDX ? UA_ITERS : 1], c[IDX ? UA_ITERS : 1];
     int total = 0;
     #pragma unroll
     for (int t = 0; t < UA_ITERS; ++t) {
         long i = i0 + t * stride;
+        // IDX: every element's slot is read beside is_first (both
+        // coalesced), so the tcount lookup does not wait for the ballots
+        if constexpr (IDX) sl[t] = (i < n) ? slot_of[i] : -1;
         bool first = (i < n) && is_first[i];
         ballots[t] = __ballot(first);
         total += __popcll(ballots[t]);
     }
     if (!total) return;
-    int base = 0;
-    if (lane == 0) base = atomicAdd(counter, total);
+    int off = 0, wtot = 0;
+    if constexpr (IDX) {
+        int ctot = 0;
+        #pragma unroll
+        for (int t = 0; t < UA_ITERS; ++t) {
+            c[t] = (ballots[t] >> lane & 1ull)
+                       ? (sl[t] >= 0 ? ix.tcount[sl[t]] : 1) : 0;
+            ctot += c[t];
+        }
+        int inc = ctot;   // inclusive wave scan of the per-thread totals
+        #pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            int v = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += v;
+        }
+        wtot = __shfl(inc, 63, 64);
+        off = inc - ctot;
+    }
+    int base = 0, obase = 0;
+    if (lane == 0) {
+        base = atomicAdd(counter, total);
+        if constexpr (IDX) obase = atomicAdd(ix.off_counter, wtot);
+    }
     base = __shfl(base, 0, 64);
+    if constexpr (IDX) off += __shfl(obase, 0, 64);
     #pragma unroll
     for (int t = 0; t < UA_ITERS; ++t) {
         u64 b = ballots[t];
@@ -269,17 +360,31 @@ __global__ void k_unique_assign(const i64* __restrict__ keys, long n,
             i64 kin = keys[i];
             if (foff) kin += foff[(int)i % F];
             unique_keys[uid] = kin;
-            int s = slot_of[i];
+            int s;
+            if constexpr (IDX) s = sl[t]; else s = slot_of[i];
             if (s >= 0) tv[s] = uid;
             else inverse[i] = uid;  // overflow winner: direct assignment
+            if constexpr (IDX) {
+                ix.seg_off[uid] = off;
+                ix.seg_cnt[uid] = c[t];
+                if (s >= 0) ix.toff[s] = off;
+                else if (off >= 0 && off < n) ix.perm[off] = (int)i;
+                if (c[t] > SEG_T) {
+                    int q = atomicAdd(ix.n_long, 1);
+                    if (q < ix.long_cap) ix.long_list[q] = uid;
+                }
+                off += c[t];
+            }
         }
         base += __popcll(b);
     }
 }
 
+// IDX: element i is filed at perm[toff[slot] + rank[i]].
+template <bool IDX>
 __global__ void k_unique_inverse(long n, const int* __restrict__ slot_of,
                                  const int* __restrict__ tv,
-                                 i64* __restrict__ inverse) {
+                                 i64* __restrict__ inverse, UIdx ix) {
     // UI_ILP independent lookups in flight per thread (2-deep load chain
     // slot_of -> tv; single-element version was latency-parked)
     const long stride = (long)gridDim.x * blockDim.x;
@@ -291,13 +396,23 @@ __global__ void k_unique_inverse(long n, const int* __restrict__ slot_of,
         s[t] = (i < n) ? slot_of[i] : -1;
     }
     int v[UI_ILP];
+    int r[IDX ? UI_ILP : 1], o[IDX ? UI_ILP : 1];
     #pragma unroll
-    for (int t = 0; t < UI_ILP; ++t)
+    for (int t = 0; t < UI_ILP; ++t) {
         v[t] = (s[t] >= 0) ? tv[s[t]] : 0;
+        if constexpr (IDX) {
+            o[t] = (s[t] >= 0) ? ix.toff[s[t]] : 0;
+            r[t] = (s[t] >= 0) ? ix.rank[i0 + t * stride] : 0;
+        }
+    }
     #pragma unroll
     for (int t = 0; t < UI_ILP; ++t) {
         long i = i0 + t * stride;
         if (i >= n) continue;
+        if constexpr (IDX) {
+            long p = (long)o[t] + r[t];
+            if (s[t] >= 0 && p >= 0 && p < n) ix.perm[p] = (int)i;
+        }
         if (s[t] >= 0) inverse[i] = (i64)v[t];
         else if (s[t] <= -2) inverse[i] = inverse[-2 - s[t]];
         // s[t] == -1: overflow winner, set by the assign kernel
@@ -959,6 +1074,191 @@ __global__ void k_reduce_counts(const i64* __restrict__ inverse, long n,
     if (i >= n) return;
     if (BAG && (bag_of[i] < 0 || bag_of[i] >= B)) return;
     atomicAdd(&counts[inverse[i]], 1ull);
+}
+
+// ------------------------------------- segmented reduce (inverted index)
+// The indexed dedup (k_unique_*<true>) files every element under its uid:
+// uid's elements are perm[seg_off[uid] .. seg_off[uid] + seg_cnt[uid]), in
+// arrival order, and long_list[0 .. *n_long) names the uids with more than
+// SEG_T elements. The gradient rows are already in memory once ([n, dim],
+// plain stores of the head backward), so the per-unique sums need no
+// atomics, no zeroed scratch and no LDS hash: every output row and count is
+// written exactly once with a plain store, rows at and beyond *u_dev as
+// zeros with count 0 (what k_reduce_reset used to leave there). The sum
+// order inside a list is arrival order, as it was with the atomics: not
+// bitwise reproducible from run to run.
+//
+// One launch, two roles, chosen per block:
+//   short (seg_cnt <= SEG_T): a G-lane group per uid, lanes over columns,
+//     SR_ILP uids' dependent chains (seg -> perm -> row) in flight per
+//     group, as k_gather_init does; the rest of a list in chunks of SR_ILP
+//     rows.
+//   long: a whole block per uid, a lane group per element and LR_ILP rows
+//     in flight per group, so a list costs ceil(len / (block / G * LR_ILP))
+//     rounds of independent loads (the next round's perm entries already
+//     in flight); then a fixed-order reduction (shuffles
+//     across the wave's groups, LDS across waves). The first ``long_blocks``
+//     blocks walk long_list with a block stride: a static grid for capture.
+//     They come first in the grid because the longest list is the kernel's
+//     critical path.
+// A uid is written by the role its CLAMPED count selects, so both roles
+// decide from the same numbers.
+//
+// Guards: seg_off / seg_cnt are clamped into [0, n], every perm entry and
+// every long_list entry is range-checked, *n_long and *u_dev are clamped.
+// An inconsistent index (only the dedup's unreachable global-table overflow
+// produces one) gives wrong sums, never an out-of-range access.
+#define SR_ILP 4
+#define LR_ILP 8
+#define SEG_BLOCK 1024
+#define SEG_LONG_BLOCKS 256
+#define SEG_MAX_DIM 128   // widest rung of the launcher's ladder (G=64, CF=2)
+
+DEV void seg_range(const int* __restrict__ seg_off,
+                   const int* __restrict__ seg_cnt, long uid, long n,
+                   int& off, int& cnt) {
+    int o = seg_off[uid], c = seg_cnt[uid];
+    o = o < 0 ? 0 : (o > n ? (int)n : o);
+    c = c < 0 ? 0 : c;
+    off = o;
+    cnt = c > n - o ? (int)(n - o) : c;
+}
+
+template <int G, int CF>
+__global__ __launch_bounds__(SEG_BLOCK)
+void k_seg_reduce(const int* __restrict__ seg_off,
+                  const int* __restrict__ seg_cnt,
+                  const int* __restrict__ perm,
+                  const int* __restrict__ long_list,
+                  const int* __restrict__ n_long, long long_cap,
+                  int long_blocks, const float* __restrict__ grads, long n,
+                  long dim, const int* __restrict__ u_dev,
+                  float* __restrict__ ugrads, u64* __restrict__ counts) {
+    __shared__ float red[SEG_BLOCK / 64][G * CF];
+    const int lane = threadIdx.x % G;
+    long u = *u_dev;
+    u = u < 0 ? 0 : (u > n ? n : u);
+
+    if ((int)blockIdx.x < long_blocks) {
+        // ---- long role
+        long nl = *n_long;
+        nl = nl < 0 ? 0 : (nl > long_cap ? long_cap : nl);
+        const int group = threadIdx.x / G;
+        constexpr int NG = SEG_BLOCK / G;
+        for (long b = blockIdx.x; b < nl; b += long_blocks) {
+            const int uid = long_list[b];
+            int off = 0, cnt = 0;
+            if (uid >= 0 && uid < u)
+                seg_range(seg_off, seg_cnt, uid, n, off, cnt);
+            if (cnt <= SEG_T) continue;   // block-uniform: the short role's
+            float acc[CF];
+            #pragma unroll
+            for (int c = 0; c < CF; ++c) acc[c] = 0.0f;
+            // the next round's perm entries are loaded before this round's
+            // rows are consumed: a round costs one load latency, not two
+            int e[LR_ILP], en[LR_ILP];
+            #pragma unroll
+            for (int t = 0; t < LR_ILP; ++t)
+                en[t] = (group * LR_ILP + t < cnt)
+                            ? perm[off + group * LR_ILP + t] : -1;
+            for (long base = group * LR_ILP; base < cnt;
+                 base += NG * LR_ILP) {
+                #pragma unroll
+                for (int t = 0; t < LR_ILP; ++t) {
+                    e[t] = (en[t] < 0 || en[t] >= n) ? -1 : en[t];
+                    const long nx = base + NG * LR_ILP + t;
+                    en[t] = (nx < cnt) ? perm[off + nx] : -1;
+                }
+                float v[LR_ILP][CF];
+                #pragma unroll
+                for (int t = 0; t < LR_ILP; ++t)
+                    #pragma unroll
+                    for (int c = 0; c < CF; ++c)
+                        v[t][c] = (e[t] >= 0 && lane + c * G < dim)
+                            ? grads[(u64)e[t] * dim + lane + c * G] : 0.0f;
+                #pragma unroll
+                for (int t = 0; t < LR_ILP; ++t)
+                    #pragma unroll
+                    for (int c = 0; c < CF; ++c) acc[c] += v[t][c];
+            }
+            #pragma unroll
+            for (int d = G; d < 64; d <<= 1)
+                #pragma unroll
+                for (int c = 0; c < CF; ++c)
+                    acc[c] += __shfl_xor(acc[c], d, 64);
+            if ((threadIdx.x & 63) < G) {
+                #pragma unroll
+                for (int c = 0; c < CF; ++c)
+                    red[threadIdx.x / 64][lane + c * G] = acc[c];
+            }
+            __syncthreads();
+            if (threadIdx.x < G * CF) {
+                float s = 0.0f;
+                #pragma unroll
+                for (int w = 0; w < SEG_BLOCK / 64; ++w)
+                    s += red[w][threadIdx.x];
+                if (threadIdx.x < dim)
+                    ugrads[(u64)uid * dim + threadIdx.x] = s;
+            }
+            if (threadIdx.x == 0) counts[uid] = (u64)cnt;
+            __syncthreads();
+        }
+        return;
+    }
+
+    // ---- short role
+    const long ngroups = (long)(gridDim.x - long_blocks) * (SEG_BLOCK / G);
+    const long g0 = ((long)(blockIdx.x - long_blocks) * SEG_BLOCK
+                     + threadIdx.x) / G;
+    int off[SR_ILP], cnt[SR_ILP], e0[SR_ILP];
+    #pragma unroll
+    for (int t = 0; t < SR_ILP; ++t) {
+        long uid = g0 + t * ngroups;
+        off[t] = 0;
+        cnt[t] = 0;
+        if (uid < u) seg_range(seg_off, seg_cnt, uid, n, off[t], cnt[t]);
+    }
+    #pragma unroll
+    for (int t = 0; t < SR_ILP; ++t) {
+        e0[t] = (cnt[t] > 0 && cnt[t] <= SEG_T) ? perm[off[t]] : -1;
+        if (e0[t] < 0 || e0[t] >= n) e0[t] = -1;
+    }
+    float acc[SR_ILP][CF];
+    #pragma unroll
+    for (int t = 0; t < SR_ILP; ++t)
+        #pragma unroll
+        for (int c = 0; c < CF; ++c)
+            acc[t][c] = (e0[t] >= 0 && lane + c * G < dim)
+                ? grads[(u64)e0[t] * dim + lane + c * G] : 0.0f;
+    #pragma unroll
+    for (int t = 0; t < SR_ILP; ++t) {
+        long uid = g0 + t * ngroups;
+        if (uid >= n || cnt[t] > SEG_T) continue;   // none / the long role's
+        for (int k = 1; k < cnt[t]; k += SR_ILP) {
+            int e[SR_ILP];
+            #pragma unroll
+            for (int q = 0; q < SR_ILP; ++q) {
+                e[q] = (k + q < cnt[t]) ? perm[off[t] + k + q] : -1;
+                if (e[q] < 0 || e[q] >= n) e[q] = -1;
+            }
+            float v[SR_ILP][CF];
+            #pragma unroll
+            for (int q = 0; q < SR_ILP; ++q)
+                #pragma unroll
+                for (int c = 0; c < CF; ++c)
+                    v[q][c] = (e[q] >= 0 && lane + c * G < dim)
+                        ? grads[(u64)e[q] * dim + lane + c * G] : 0.0f;
+            #pragma unroll
+            for (int q = 0; q < SR_ILP; ++q)
+                #pragma unroll
+                for (int c = 0; c < CF; ++c) acc[t][c] += v[q][c];
+        }
+        #pragma unroll
+        for (int c = 0; c < CF; ++c)
+            if (lane + c * G < dim)
+                ugrads[(u64)uid * dim + lane + c * G] = acc[t][c];
+        if (lane == 0) counts[uid] = (u64)cnt[t];
+    }
 }
 
 // ------------------------------------------------- pooled weight gradient
@@ -1668,12 +1968,12 @@ static void pool_lookup_dispatch(const float* rows, long dim, long nnz,
 #undef LAUNCH_LOOKUP
 }
 
-extern "C" {
-
-void emb_unique(const i64* keys, long n, u64* tk, int* tv, long cap,
-                int* slot_of, unsigned char* is_first, i64* unique_keys,
-                i64* inverse, int* counter, const i64* foff, int F,
-                hipStream_t stream) {
+template <bool IDX>
+static void unique_launch(const i64* keys, long n, u64* tk, int* tv, long cap,
+                          int* slot_of, unsigned char* is_first,
+                          i64* unique_keys, i64* inverse, int* counter,
+                          const i64* foff, int F, const UIdx& ix,
+                          hipStream_t stream) {
     // fill kernel, not hipMemsetAsync: memsets issued here were NOT
     // replayed inside hipGraph captures (scratch kept stale keys across
     // replays until the probe loops hung); kernels always capture. One
@@ -1681,19 +1981,75 @@ void emb_unique(const i64* keys, long n, u64* tk, int* tv, long cap,
     // launch/ramp in the step (profiles/step_attrib_r2.txt)
     {
         long mx = cap > n ? cap : n;
-        k_unique_reset<<<(int)((mx + 255) / 256), 256, 0, stream>>>(
-            tk, cap, is_first, n, counter);
+        k_unique_reset<IDX><<<(int)((mx + 255) / 256), 256, 0, stream>>>(
+            tk, cap, is_first, n, counter, ix);
     }
     long mask = cap - 1;
-    k_unique_insert<<<grid1d(n), BLOCK, 0, stream>>>(keys, n, tk, mask,
-                                                     slot_of, is_first,
-                                                     foff, F);
+    k_unique_insert<IDX><<<grid1d(n), BLOCK, 0, stream>>>(
+        keys, n, tk, mask, slot_of, is_first, foff, F, ix);
     int ga = grid1d((n + UA_ITERS - 1) / UA_ITERS);
     int gi = grid1d((n + UI_ILP - 1) / UI_ILP);
-    k_unique_assign<<<ga, BLOCK, 0, stream>>>(keys, n, slot_of, is_first,
-                                              tv, unique_keys, counter,
-                                              inverse, foff, F);
-    k_unique_inverse<<<gi, BLOCK, 0, stream>>>(n, slot_of, tv, inverse);
+    k_unique_assign<IDX><<<ga, BLOCK, 0, stream>>>(
+        keys, n, slot_of, is_first, tv, unique_keys, counter, inverse, foff,
+        F, ix);
+    k_unique_inverse<IDX><<<gi, BLOCK, 0, stream>>>(n, slot_of, tv, inverse,
+                                                    ix);
+}
+
+extern "C" {
+
+void emb_unique(const i64* keys, long n, u64* tk, int* tv, long cap,
+                int* slot_of, unsigned char* is_first, i64* unique_keys,
+                i64* inverse, int* counter, const i64* foff, int F,
+                hipStream_t stream) {
+    unique_launch<false>(keys, n, tk, tv, cap, slot_of, is_first,
+                         unique_keys, inverse, counter, foff, F, UIdx{},
+                         stream);
+}
+
+// The same dedup, which also files every element under its uid (the
+// inverted index that emb_reduce_by_index sums through). tcount/toff [cap]
+// and rank [n] are scratch; long_list has long_cap >= n / (SEG_T + 1) + 1
+// entries, which no batch of n elements can exceed.
+void emb_unique_indexed(const i64* keys, long n, u64* tk, int* tv, long cap,
+                        int* slot_of, unsigned char* is_first,
+                        i64* unique_keys, i64* inverse, int* counter,
+                        const i64* foff, int F, int* tcount, int* toff,
+                        int* rank, int* seg_off, int* seg_cnt, int* perm,
+                        int* long_list, long long_cap, int* off_counter,
+                        int* n_long, hipStream_t stream) {
+    UIdx ix{tcount, toff, rank, seg_off, seg_cnt, perm, long_list,
+            off_counter, n_long, long_cap};
+    unique_launch<true>(keys, n, tk, tv, cap, slot_of, is_first, unique_keys,
+                        inverse, counter, foff, F, ix, stream);
+}
+
+int emb_seg_threshold() { return SEG_T; }
+int emb_seg_max_dim() { return SEG_MAX_DIM; }
+
+// Per-unique sums and counts through the inverted index: what
+// emb_reduce_by_inverse gives for u = n, without its reset launch.
+// dim <= SEG_MAX_DIM (the caller checks).
+void emb_reduce_by_index(const int* seg_off, const int* seg_cnt,
+                         const int* perm, const int* long_list,
+                         const int* n_long, long long_cap,
+                         const float* grads, long n, long dim,
+                         const int* u_dev, float* ugrads, u64* counts,
+                         hipStream_t stream) {
+    if (n == 0) return;
+    int lb = (int)(long_cap < SEG_LONG_BLOCKS ? long_cap : SEG_LONG_BLOCKS);
+    long groups = (n + SR_ILP - 1) / SR_ILP;
+#define LAUNCH_SEG(G, CF)                                                   \
+    k_seg_reduce<G, CF>                                                     \
+        <<<lb + cdiv(groups * G, SEG_BLOCK), SEG_BLOCK, 0, stream>>>(       \
+            seg_off, seg_cnt, perm, long_list, n_long, long_cap, lb, grads, \
+            n, dim, u_dev, ugrads, counts)
+    // G as in emb_gather_init: 16 lanes up to dim 32, a full wave above
+    if (dim <= 16) LAUNCH_SEG(16, 1);
+    else if (dim <= 32) LAUNCH_SEG(16, 2);
+    else if (dim <= 64) LAUNCH_SEG(64, 1);
+    else LAUNCH_SEG(64, 2);
+#undef LAUNCH_SEG
 }
 
 void emb_ht_lookup(u64* tk, int* tv, long cap, const i64* keys, long n,

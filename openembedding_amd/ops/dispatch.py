@@ -55,6 +55,50 @@ def reduce_by_inverse(inverse: torch.Tensor, grads: torch.Tensor, u: int
     return ugrads, counts
 
 
+def seg_reduce_covers(grads: torch.Tensor) -> bool:
+    """True when ``reduce_by_index`` has a kernel for ``grads``: float32 on
+    the GPU with a dim on the kernel's ladder. Everything else (float64
+    variables, wider rows, CPU tensors) keeps ``reduce_by_inverse``."""
+    if not (_use_hip(grads) and grads.dtype == torch.float32):
+        return False
+    ext = require_hip()
+    return ext is not None and grads.shape[1] <= ext.seg_reduce_max_dim()
+
+
+def reduce_by_index(index, grads: torch.Tensor, u_dev
+                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``reduce_by_inverse(inverse, grads, n)`` summed through the batch's
+    inverted index instead of atomics.
+
+    index = (seg_off, seg_cnt, perm, long_list, n_long) as
+    ``unique_bounded_indexed`` returns it: uid's elements are
+    ``perm[seg_off[uid] : seg_off[uid] + seg_cnt[uid]]``; ``u_dev`` is the
+    live unique count (int32 [1] tensor, or an int on the torch path).
+    grads [n, dim] -> (ugrads [n, dim], counts int64 [n]); rows at and
+    beyond ``u_dev`` are zero with count 0. Rows are added in list order
+    (arrival order on the GPU: not bitwise reproducible from run to run,
+    like the atomic reduce it replaces)."""
+    seg_off, seg_cnt, perm, long_list, n_long = index
+    if seg_reduce_covers(grads):
+        return require_hip().reduce_by_index(seg_off, seg_cnt, perm,
+                                             long_list, n_long, grads, u_dev)
+    n = grads.shape[0]
+    u = int(u_dev)
+    dev = grads.device
+    cnt = seg_cnt[:u].to(dev, torch.int64)
+    start = seg_off[:u].to(dev, torch.int64)
+    uid = torch.repeat_interleave(torch.arange(u, device=dev), cnt)
+    first = torch.cumsum(cnt, 0) - cnt      # of each list in the flat walk
+    pos = (torch.arange(uid.numel(), device=dev)
+           + torch.repeat_interleave(start - first, cnt))
+    elems = perm.to(dev, torch.int64).index_select(0, pos)
+    ugrads = torch.zeros((n, grads.shape[1]), dtype=grads.dtype, device=dev)
+    ugrads.index_add_(0, uid, grads.index_select(0, elems))
+    counts = torch.zeros(n, dtype=torch.int64, device=dev)
+    counts[:u] = cnt
+    return ugrads, counts
+
+
 # ------------------------------------------------------------ multi-hot bags
 
 POOL_MODES = {"sum": 0, "mean": 1, "sqrtn": 2}

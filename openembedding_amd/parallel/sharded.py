@@ -33,6 +33,22 @@ from ..utils.metrics import REGISTRY, stage_timer
 from . import comm
 
 
+# Segmented reduce through the inverted index of the batch (ops/csrc/
+# embops.hip, "segmented reduce"): on by default; OEAMD_SEG_REDUCE=0 keeps
+# the atomic reduce-by-inverse everywhere (A/B runs, fallback switch).
+_SEG_REDUCE = os.environ.get("OEAMD_SEG_REDUCE", "1") != "0"
+
+
+def _unique_bounded(ext, flat: torch.Tensor, field_offsets):
+    """(uk_buf, inverse, u_dev, index) of the bounded dedup; ``index`` is
+    the inverted index ``ops.reduce_by_index`` takes, or None when the
+    segmented reduce is switched off."""
+    if not _SEG_REDUCE:
+        return (*ext.unique_bounded(flat, field_offsets), None)
+    r = ext.unique_bounded_indexed(flat, field_offsets)
+    return r[0], r[1], r[2], tuple(r[3:])
+
+
 class _PaddedPlan:
     """Fixed-capacity wire plan of the sync-free padded all-to-all.
 
@@ -103,6 +119,10 @@ class PullHandle:
     # [nnz, dim] rows the pool read
     bag_scale: Optional[torch.Tensor] = None
     pooled_rows: Optional[torch.Tensor] = None
+    # inverted index of ``inverse`` (seg_off, seg_cnt, perm, long_list,
+    # n_long; all device int32), set by the flat bounded and padded pulls:
+    # push then sums through it instead of reduce-by-inverse
+    index: Optional[tuple] = None
 
 
 class ShardedVariable:
@@ -205,10 +225,11 @@ class ShardedVariable:
         """Single-GPU sync-free pull: bounded unique buffer + fused
         gather/init/scatter; zero host round-trips (hipGraph-capturable)."""
         ext = self.shard.ext
-        uk_buf, inverse, u_dev = ext.unique_bounded(flat, field_offsets)
+        uk_buf, inverse, u_dev, index = _unique_bounded(ext, flat,
+                                                        field_offsets)
         out, slots = self.shard.pull_bounded(uk_buf, u_dev, inverse)
         h = PullHandle(shape=indices.shape, unique=uk_buf, inverse=inverse,
-                       bounded=True, u_dev=u_dev, slots=slots)
+                       bounded=True, u_dev=u_dev, slots=slots, index=index)
         return out.view(*indices.shape, self.shard.dim), h
 
     def pull_pooled(self, values: torch.Tensor, offsets: torch.Tensor,
@@ -396,9 +417,11 @@ class ShardedVariable:
         if plan is None:
             return None
         gpu = getattr(self.shard, "pull_bounded", None) is not None
+        index = None
         if gpu:
             ext = self.shard.ext
-            uk_buf, inverse, u_dev = ext.unique_bounded(flat, field_offsets)
+            uk_buf, inverse, u_dev, index = _unique_bounded(ext, flat,
+                                                            field_offsets)
             ext.bucketize_pad(uk_buf, u_dev, world, plan.cap,
                               plan.send_keys, plan.send_src, plan.pos_of,
                               plan.counts, plan.overflow)
@@ -409,7 +432,7 @@ class ShardedVariable:
         REGISTRY.add("pull_indices", n)
         REGISTRY.add("pull_wire_keys", plan.send_keys.numel())
         h = PullHandle(shape=indices.shape, unique=uk_buf, inverse=inverse,
-                       u_dev=u_dev, padded=True, plan=plan)
+                       u_dev=u_dev, padded=True, plan=plan, index=index)
         recv_keys = comm.all_to_all_equal(plan.send_keys, world)
         if gpu:
             uk2_buf, inv2, u2_dev = ext.unique_bounded(recv_keys)
@@ -571,8 +594,11 @@ class ShardedVariable:
         """grads: [*shape, dim] gradient of the pulled weights."""
         dim = self.shard.dim
         g = grads.reshape(-1, dim)
-        ugrads, counts = ops.reduce_by_inverse(h.inverse, g,
-                                               h.unique.numel())
+        if h.index is not None and ops.seg_reduce_covers(g):
+            ugrads, counts = ops.reduce_by_index(h.index, g, h.u_dev)
+        else:
+            ugrads, counts = ops.reduce_by_inverse(h.inverse, g,
+                                                   h.unique.numel())
         self._apply_reduced(h, ugrads, counts)
 
     def push_pooled(self, h: PullHandle, grad_out: torch.Tensor,
