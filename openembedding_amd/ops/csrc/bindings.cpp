@@ -67,6 +67,16 @@ void emb_pool_wgrad(const float*, long, long, const i64*, long, const void*,
 void emb_pool_lookup(const float*, long, long, const i64*, long, const i64*,
                      long, int, const float*, const u64*, const int*, long,
                      const unsigned char*, long, float*, hipStream_t_);
+long emb_quant_stride(int, long);
+void emb_quantize_rows(int, const float*, long, long, const i64*, void*,
+                       long, hipStream_t_);
+void emb_pool_lookup_q(int, const void*, long, long, const i64*, long,
+                       const i64*, long, int, const float*, const u64*,
+                       const int*, long, const unsigned char*, long, float*,
+                       hipStream_t_);
+void emb_gather_lookup_q(int, const void*, long, long, const i64*, long,
+                         const u64*, const int*, long, const unsigned char*,
+                         long, float*, hipStream_t_);
 void emb_apply_optimizer(int, float*, float*, long, long, const i64*, long,
                          const float*, const u64*, const float*, const int*,
                          hipStream_t_);
@@ -727,6 +737,164 @@ torch::Tensor pool_lookup(torch::Tensor rows, torch::Tensor values,
     return out;
 }
 
+// ---- quantized serving tables -----------------------------------------
+// slab: uint8 [R, stride] packed rows, stride == emb_quant_stride(fmt, dim),
+// fmt 0 = int8 (codes + fp32 scale + fp32 lo), 1 = fp16; rows are read and
+// written as dwords, so the slab starts on a 4-byte boundary.
+
+void check_slab(const torch::Tensor& slab, int64_t dim, int64_t fmt,
+                const char* who) {
+    TORCH_CHECK(slab.is_cuda() && slab.is_contiguous()
+                && slab.dtype() == torch::kUInt8 && slab.dim() == 2,
+                who, ": slab must be a contiguous uint8 [R, stride] GPU "
+                "tensor");
+    TORCH_CHECK(fmt == 0 || fmt == 1, who, ": fmt must be 0 (int8) or 1 "
+                "(fp16)");
+    TORCH_CHECK(dim >= 1, who, ": dim must be >= 1");
+    TORCH_CHECK(slab.size(1) == emb_quant_stride((int)fmt, (long)dim), who,
+                ": slab stride ", slab.size(1), " is not the stride ",
+                emb_quant_stride((int)fmt, (long)dim), " of this format and "
+                "dim");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(slab.data_ptr()) % 4 == 0, who,
+                ": slab must be 4-byte aligned");
+}
+
+// the key -> row table of a lookup: exactly one of (tk, tv) — hash, int64 /
+// int32 [cap], cap a power of two — or (valid uint8 [cap], shard_num)
+struct KeyTable {
+    const u64* tk = nullptr;
+    const int* tv = nullptr;
+    const uint8_t* valid = nullptr;
+    long cap = 0;
+};
+
+KeyTable check_key_table(const OptTensor& tk, const OptTensor& tv,
+                         const OptTensor& valid, int64_t shard_num,
+                         const torch::Device& dev, const char* who) {
+    KeyTable t;
+    const bool hash = tk.has_value() || tv.has_value();
+    TORCH_CHECK(hash != valid.has_value(), who,
+                ": pass either (tk, tv) or (valid, shard_num)");
+    if (hash) {
+        TORCH_CHECK(tk.has_value() && tv.has_value(), who,
+                    ": tk and tv go together");
+        CHECK_GPU(*tk); CHECK_CONT(*tk);
+        CHECK_GPU(*tv); CHECK_CONT(*tv);
+        t.cap = tk->numel();
+        TORCH_CHECK(tk->dtype() == torch::kInt64
+                    && tv->dtype() == torch::kInt32 && tv->numel() == t.cap
+                    && t.cap >= 1 && (t.cap & (t.cap - 1)) == 0
+                    && tk->device() == dev && tv->device() == dev, who,
+                    ": tk int64 / tv int32 [cap], cap a power of two, on "
+                    "the slab's device");
+        t.tk = (const u64*)tk->data_ptr<i64>();
+        t.tv = tv->data_ptr<int>();
+    } else {
+        CHECK_GPU(*valid); CHECK_CONT(*valid);
+        t.cap = valid->numel();
+        TORCH_CHECK(valid->dtype() == torch::kUInt8
+                    && valid->device() == dev, who,
+                    ": valid must be uint8 [cap] on the slab's device");
+        TORCH_CHECK(shard_num >= 1, who, ": shard_num must be >= 1");
+        t.valid = valid->data_ptr<uint8_t>();
+    }
+    return t;
+}
+
+// Quantize fp32 rows w [n, dim] into rows slots[i] of the slab, in place.
+// A slot < 0 or >= R is skipped. Two source rows naming one slot in one
+// call is the caller's error (the two groups race on the row); callers
+// deduplicate first, as QuantizedShard.import_rows does (last one wins).
+// Values are not validated here (non-finite rows, fp16 overflow): that is
+// the host-side check of the import.
+void quantize_rows(torch::Tensor w, torch::Tensor slots, torch::Tensor slab,
+                   int64_t fmt) {
+    CHECK_GPU(w); CHECK_CONT(w);
+    CHECK_GPU(slots); CHECK_CONT(slots);
+    TORCH_CHECK(w.dtype() == torch::kFloat32 && w.dim() == 2
+                && w.size(1) >= 1,
+                "quantize_rows: w must be float32 [n, dim >= 1]");
+    check_slab(slab, w.size(1), fmt, "quantize_rows");
+    TORCH_CHECK(slots.dtype() == torch::kInt64 && slots.dim() == 1
+                && slots.numel() == w.size(0),
+                "quantize_rows: slots must be int64 [n]");
+    TORCH_CHECK(w.device() == slab.device()
+                && slots.device() == slab.device(),
+                "quantize_rows: w and slots must be on the slab's device");
+    const c10::cuda::CUDAGuard guard(slab.device());
+    emb_quantize_rows((int)fmt, w.data_ptr<float>(), w.size(0), w.size(1),
+                      slots.data_ptr<i64>(), slab.data_ptr(), slab.size(0),
+                      cur_stream());
+}
+
+// pool_lookup over a packed slab: values int64 [nnz_cap] keys, offsets
+// int64 [B+1], optional weights f32 [nnz_cap] -> out f32 [B, dim] in one
+// launch, the table only read.
+torch::Tensor pool_lookup_q(torch::Tensor slab, int64_t dim, int64_t fmt,
+                            torch::Tensor values, torch::Tensor offsets,
+                            int64_t mode, OptTensor weights, OptTensor tk,
+                            OptTensor tv, OptTensor valid,
+                            int64_t shard_num) {
+    check_slab(slab, dim, fmt, "pool_lookup_q");
+    CHECK_GPU(values); CHECK_CONT(values);
+    CHECK_GPU(offsets); CHECK_CONT(offsets);
+    TORCH_CHECK(values.dtype() == torch::kInt64 && values.dim() == 1,
+                "pool_lookup_q: values must be int64 [nnz]");
+    TORCH_CHECK(offsets.dtype() == torch::kInt64 && offsets.dim() == 1
+                && offsets.numel() >= 1,
+                "pool_lookup_q: offsets must be int64 [B+1]");
+    TORCH_CHECK(mode >= 0 && mode <= 2, "pool_lookup_q: bad mode");
+    TORCH_CHECK(values.device() == slab.device()
+                && offsets.device() == slab.device(),
+                "pool_lookup_q: values and offsets must be on the table's "
+                "device");
+    long nnz = values.numel();
+    const float* w_ptr = nullptr;
+    if (weights.has_value()) {
+        CHECK_GPU(*weights); CHECK_CONT(*weights);
+        TORCH_CHECK(weights->dtype() == torch::kFloat32
+                    && weights->dim() == 1 && weights->numel() == nnz
+                    && weights->device() == slab.device(),
+                    "pool_lookup_q: weights must be float32 [nnz]");
+        w_ptr = weights->data_ptr<float>();
+    }
+    const KeyTable t = check_key_table(tk, tv, valid, shard_num,
+                                       slab.device(), "pool_lookup_q");
+    const c10::cuda::CUDAGuard guard(slab.device());
+    long B = offsets.numel() - 1;
+    auto out = torch::empty({B, dim},
+                            slab.options().dtype(torch::kFloat32));
+    emb_pool_lookup_q((int)fmt, slab.data_ptr(), slab.size(0), dim,
+                      values.data_ptr<i64>(), nnz, offsets.data_ptr<i64>(),
+                      B, (int)mode, w_ptr, t.tk, t.tv, t.cap, t.valid,
+                      (long)shard_num, out.data_ptr<float>(), cur_stream());
+    return out;
+}
+
+// flat read over a packed slab: keys int64 [n] -> f32 [n, dim] in one
+// launch; zeros for key -1, an absent key or an out-of-range table entry
+torch::Tensor gather_lookup_q(torch::Tensor slab, int64_t dim, int64_t fmt,
+                              torch::Tensor keys, OptTensor tk, OptTensor tv,
+                              OptTensor valid, int64_t shard_num) {
+    check_slab(slab, dim, fmt, "gather_lookup_q");
+    CHECK_GPU(keys); CHECK_CONT(keys);
+    TORCH_CHECK(keys.dtype() == torch::kInt64 && keys.dim() == 1
+                && keys.device() == slab.device(),
+                "gather_lookup_q: keys must be int64 [n] on the table's "
+                "device");
+    const KeyTable t = check_key_table(tk, tv, valid, shard_num,
+                                       slab.device(), "gather_lookup_q");
+    const c10::cuda::CUDAGuard guard(slab.device());
+    long n = keys.numel();
+    auto out = torch::empty({n, dim},
+                            slab.options().dtype(torch::kFloat32));
+    emb_gather_lookup_q((int)fmt, slab.data_ptr(), slab.size(0), dim,
+                        keys.data_ptr<i64>(), n, t.tk, t.tv, t.cap, t.valid,
+                        (long)shard_num, out.data_ptr<float>(),
+                        cur_stream());
+    return out;
+}
+
 void mask_tail(torch::Tensor keys, torch::Tensor grads, torch::Tensor counts,
                OptTensor u_dev) {
     CHECK_GPU(keys); CHECK_CONT(keys); CHECK_CONT(grads); CHECK_CONT(counts);
@@ -1377,6 +1545,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("rows"), pybind11::arg("values"),
           pybind11::arg("offsets"), pybind11::arg("mode"),
           pybind11::arg("weights") = pybind11::none(),
+          pybind11::arg("tk") = pybind11::none(),
+          pybind11::arg("tv") = pybind11::none(),
+          pybind11::arg("valid") = pybind11::none(),
+          pybind11::arg("shard_num") = 1);
+    m.def("quantize_rows", &quantize_rows,
+          "fp32 rows -> packed rows at the given slots of a slab (slots "
+          "unique within a call)",
+          pybind11::arg("w"), pybind11::arg("slots"), pybind11::arg("slab"),
+          pybind11::arg("fmt"));
+    m.def("pool_lookup_q", &pool_lookup_q,
+          "read-only pooled lookup over a packed slab, keys -> pooled fp32 "
+          "rows in one launch (hash: tk/tv; array: valid/shard_num)",
+          pybind11::arg("slab"), pybind11::arg("dim"), pybind11::arg("fmt"),
+          pybind11::arg("values"), pybind11::arg("offsets"),
+          pybind11::arg("mode"),
+          pybind11::arg("weights") = pybind11::none(),
+          pybind11::arg("tk") = pybind11::none(),
+          pybind11::arg("tv") = pybind11::none(),
+          pybind11::arg("valid") = pybind11::none(),
+          pybind11::arg("shard_num") = 1);
+    m.def("gather_lookup_q", &gather_lookup_q,
+          "flat read over a packed slab, keys -> fp32 rows in one launch",
+          pybind11::arg("slab"), pybind11::arg("dim"), pybind11::arg("fmt"),
+          pybind11::arg("keys"),
           pybind11::arg("tk") = pybind11::none(),
           pybind11::arg("tv") = pybind11::none(),
           pybind11::arg("valid") = pybind11::none(),

@@ -869,6 +869,309 @@ __global__ void k_pool_lookup(const float* __restrict__ rows, long dim,
                                                  resolve);
 }
 
+// ------------------------------------------------- quantized serving tables
+// A read-only table stored as packed rows: a uint8 slab [R, stride] with
+// stride % 4 == 0, every row a whole number of dwords (docs/kernels.md has
+// the byte layout; ops/dispatch.py quantize_rows / dequantize_rows is the
+// same definition in torch and the oracle of everything below).
+//   QF_INT8: dim unsigned codes, zero pad to a dword, fp32 scale, fp32 lo;
+//            x^ = lo + scale * (float)code (one multiply, then one add)
+//   QF_FP16: dim IEEE halves, zero pad to a dword; x^ = (float)half
+// All arithmetic is fp32 op for op (-ffp-contract=off, correctly rounded
+// division), so a slab written here is byte-identical to the oracle's and
+// a lookup is bit-identical to dequantize-then-pool on the CPU.
+//
+// The lookups below carry their own accumulate body instead of sharing
+// pool_accumulate through a row-format policy: a lane's fragment here is a
+// dword of 4 (or 2) consecutive columns with a per-row scale/lo, not one
+// fp32 column, so the accumulator shape, the column index and the store
+// all differ, and keeping the bodies apart leaves the fp32 instantiations
+// of k_pool_fwd / k_pool_lookup untouched. What defines the result is
+// shared: the resolvers, pool_clamp, pool_scale / pool_wscale, the miss and
+// empty-bag rules and the element-order plain adds.
+
+enum { QF_INT8 = 0, QF_FP16 = 1 };
+
+template <int FMT> struct QFmt;
+template <> struct QFmt<QF_INT8> {
+    static constexpr int CPD = 4;    // columns per dword
+    static __host__ __device__ long code_dwords(long dim) {
+        return (dim + 3) / 4;
+    }
+    static __host__ __device__ long stride(long dim) {
+        return 4 * code_dwords(dim) + 8;
+    }
+};
+template <> struct QFmt<QF_FP16> {
+    static constexpr int CPD = 2;
+    static __host__ __device__ long code_dwords(long dim) {
+        return (dim + 1) / 2;
+    }
+    static __host__ __device__ long stride(long dim) {
+        return 4 * code_dwords(dim);
+    }
+};
+
+DEV unsigned int q_half_bits(float x) {
+    return (unsigned int)__builtin_bit_cast(unsigned short, (_Float16)x);
+}
+DEV float q_half_value(unsigned int bits) {
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)bits);
+}
+
+// columns [CPD * d, CPD * d + CPD) of a row from its dword ``word``
+template <int FMT>
+DEV void q_unpack(unsigned int word, float scale, float lo,
+                  float (&x)[QFmt<FMT>::CPD]) {
+    if constexpr (FMT == QF_INT8) {
+        #pragma unroll
+        for (int i = 0; i < 4; ++i)
+            x[i] = lo + scale * (float)((word >> (8 * i)) & 0xffu);
+    } else {
+        x[0] = q_half_value(word & 0xffffu);
+        x[1] = q_half_value(word >> 16);
+    }
+}
+
+// One G-lane group per source row: a shuffle min/max tree over the row
+// (int8), then every lane packs whole dwords — four codes or two halves,
+// pad columns as zero bytes — and lane 0 adds the scale and lo dwords.
+// Source row i goes to slab row slots[i]; a slot outside [0, R) is
+// skipped. Two rows of one call naming the same slot race (caller's error).
+// lo is stored as min(row) + 0.0f, which turns a -0.0 minimum into +0.0:
+// which zero a min over both signs returns depends on the reduction order,
+// and x^ is the same for either.
+template <int FMT, int G>
+__global__ void k_quantize_rows(const float* __restrict__ w, long n,
+                                long dim, const i64* __restrict__ slots,
+                                unsigned int* __restrict__ slab, long R) {
+    const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    const int lane = threadIdx.x % G;
+    if (i >= n) return;                 // whole groups leave together
+    const i64 slot = slots[i];
+    if (slot < 0 || slot >= (i64)R) return;
+    const float* __restrict__ src = w + (u64)i * dim;
+    const long ndw = QFmt<FMT>::code_dwords(dim);
+    unsigned int* __restrict__ dst =
+        slab + (u64)slot * (QFmt<FMT>::stride(dim) / 4);
+    float lo = 0.0f, scale = 0.0f;
+    if constexpr (FMT == QF_INT8) {
+        float mn = src[0], mx = src[0];
+        for (long c = lane; c < dim; c += G) {
+            const float v = src[c];
+            mn = fminf(mn, v);
+            mx = fmaxf(mx, v);
+        }
+        #pragma unroll
+        for (int o = G / 2; o > 0; o >>= 1) {
+            mn = fminf(mn, __shfl_xor(mn, o, G));
+            mx = fmaxf(mx, __shfl_xor(mx, o, G));
+        }
+        lo = mn + 0.0f;
+        scale = (mx - lo) / 255.0f;
+        if (scale < 1.17549435e-38f) scale = 0.0f;   // FLT_MIN
+    }
+    for (long d = lane; d < ndw; d += G) {
+        unsigned int word = 0;
+        #pragma unroll
+        for (int k = 0; k < QFmt<FMT>::CPD; ++k) {
+            const long c = d * QFmt<FMT>::CPD + k;
+            if (c >= dim) continue;
+            unsigned int bits;
+            if constexpr (FMT == QF_INT8) {
+                float q = 0.0f;
+                if (scale != 0.0f) {
+                    q = rintf((src[c] - lo) / scale);
+                    q = fminf(fmaxf(q, 0.0f), 255.0f);
+                }
+                bits = (unsigned int)q;
+                word |= bits << (8 * k);
+            } else {
+                bits = q_half_bits(src[c]);
+                word |= bits << (16 * k);
+            }
+        }
+        dst[d] = word;
+    }
+    if constexpr (FMT == QF_INT8) {
+        if (lane == 0) {
+            dst[ndw] = __float_as_uint(scale);
+            dst[ndw + 1] = __float_as_uint(lo);
+        }
+    }
+}
+
+// The accumulate body of k_pool_lookup_q: pool_accumulate's plan — lane l
+// resolves element j0+l, the next chunk's probes are issued before this
+// chunk's row reads, rows broadcast through __shfl and read PF_ILP at a
+// time — over packed rows. A lane owns dword lane + k*G of a row (PF_CF of
+// them), i.e. CPD consecutive columns per fragment, loaded as one dword;
+// the row's scale and lo are two more dword loads per row, the same
+// address in every lane. ``sdw`` is the row stride in dwords.
+template <int FMT, int G, int PF_CF, int PF_ILP, bool WEIGHTED,
+          typename Resolve>
+DEV void pool_accumulate_q(const unsigned int* __restrict__ slab, long dim,
+                           long s, long e, long b, int lane, int mode,
+                           const float* __restrict__ weights,
+                           float* __restrict__ out, const Resolve& resolve) {
+    constexpr int CPD = QFmt<FMT>::CPD;
+    const long ndw = QFmt<FMT>::code_dwords(dim);
+    const long sdw = QFmt<FMT>::stride(dim) / 4;
+    float scale = 1.0f;
+    if constexpr (!WEIGHTED) scale = pool_scale(mode, e - s);
+    for (long d0 = 0; d0 < ndw; d0 += (long)G * PF_CF) {
+        float acc[PF_CF][CPD];
+        #pragma unroll
+        for (int k = 0; k < PF_CF; ++k)
+            #pragma unroll
+            for (int i = 0; i < CPD; ++i) acc[k][i] = 0.0f;
+        long myrow = resolve(s + lane, e);
+        float myw = 0.0f, den = 0.0f;
+        if constexpr (WEIGHTED)
+            if (s + lane < e) myw = weights[s + lane];
+        for (long j0 = s; j0 < e; j0 += G) {
+            const long nextrow = resolve(j0 + G + lane, e);
+            float nextw = 0.0f;
+            if constexpr (WEIGHTED)
+                if (j0 + G + lane < e) nextw = weights[j0 + G + lane];
+            const int cnt = (int)((e - j0) < G ? (e - j0) : G);
+            for (int t0 = 0; t0 < cnt; t0 += PF_ILP) {
+                long row[PF_ILP];
+                float wt[WEIGHTED ? PF_ILP : 1];
+                #pragma unroll
+                for (int t = 0; t < PF_ILP; ++t) {  // t0 + t < G always
+                    row[t] = __shfl(myrow, t0 + t, G);
+                    if constexpr (WEIGHTED) wt[t] = __shfl(myw, t0 + t, G);
+                }
+                // Every load is unconditional, from a clamped in-range
+                // address (a miss reads row 0, a lane past the row its last
+                // dword; the launcher never starts this kernel with R == 0),
+                // and what must not count is zeroed afterwards: word 0,
+                // scale 0, lo 0 -> x^ = 0. Loads under a per-row branch
+                // made the compiler wait for each row's scale / lo before
+                // issuing the next row's loads (PF_ILP serial round trips
+                // instead of one).
+                unsigned int word[PF_ILP][PF_CF];
+                float rs[PF_ILP], rl[PF_ILP];
+                #pragma unroll
+                for (int t = 0; t < PF_ILP; ++t) {
+                    const unsigned int* __restrict__ r =
+                        slab + (u64)(row[t] >= 0 ? row[t] : 0) * sdw;
+                    #pragma unroll
+                    for (int k = 0; k < PF_CF; ++k) {
+                        const long d = d0 + lane + (long)k * G;
+                        word[t][k] = r[d < ndw ? d : ndw - 1];
+                    }
+                    rs[t] = 0.0f;
+                    rl[t] = 0.0f;
+                    if constexpr (FMT == QF_INT8) {
+                        rs[t] = __uint_as_float(r[ndw]);
+                        rl[t] = __uint_as_float(r[ndw + 1]);
+                    }
+                }
+                #pragma unroll
+                for (int t = 0; t < PF_ILP; ++t) {
+                    const bool hit = row[t] >= 0;
+                    #pragma unroll
+                    for (int k = 0; k < PF_CF; ++k) {
+                        const long d = d0 + lane + (long)k * G;
+                        word[t][k] = (hit && d < ndw) ? word[t][k] : 0u;
+                    }
+                    rs[t] = hit ? rs[t] : 0.0f;
+                    rl[t] = hit ? rl[t] : 0.0f;
+                }
+                #pragma unroll
+                for (int t = 0; t < PF_ILP; ++t) {
+                    if (t0 + t < cnt) {
+                        #pragma unroll
+                        for (int k = 0; k < PF_CF; ++k) {
+                            float x[CPD];
+                            q_unpack<FMT>(word[t][k], rs[t], rl[t], x);
+                            #pragma unroll
+                            for (int i = 0; i < CPD; ++i) {
+                                if constexpr (WEIGHTED)
+                                    acc[k][i] += wt[t] * x[i];
+                                else
+                                    acc[k][i] += x[i];
+                            }
+                        }
+                        if constexpr (WEIGHTED)
+                            den += (mode == POOL_SQRTN) ? wt[t] * wt[t]
+                                                        : wt[t];
+                    }
+                }
+            }
+            myrow = nextrow;
+            if constexpr (WEIGHTED) myw = nextw;
+        }
+        if constexpr (WEIGHTED) scale = pool_wscale(mode, den);
+        #pragma unroll
+        for (int k = 0; k < PF_CF; ++k) {
+            const long c = (d0 + lane + (long)k * G) * CPD;
+            #pragma unroll
+            for (int i = 0; i < CPD; ++i)
+                if (c + i < dim) out[(u64)b * dim + c + i] = acc[k][i] * scale;
+        }
+    }
+}
+
+// Read-only pooled lookup over a packed slab: k_pool_lookup with the row
+// read replaced by a dequantizing dword read. values [nnz] keys and
+// offsets [B+1] -> out [B, dim] fp32, one launch, the table only read.
+template <int FMT, int G, int PF_CF, int PF_ILP, bool WEIGHTED,
+          typename Resolve>
+__global__ void k_pool_lookup_q(const unsigned int* __restrict__ slab,
+                                long dim, long nnz,
+                                const i64* __restrict__ offsets, long B,
+                                int mode, const float* __restrict__ weights,
+                                float* __restrict__ out, Resolve resolve) {
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long b = tid / G;
+    const int lane = threadIdx.x % G;
+    if (b >= B) return;
+    const long s = pool_clamp(offsets[b], nnz);
+    long e = pool_clamp(offsets[b + 1], nnz);
+    if (e < s) e = s;
+    pool_accumulate_q<FMT, G, PF_CF, PF_ILP, WEIGHTED>(
+        slab, dim, s, e, b, lane, mode, weights, out, resolve);
+}
+
+// The flat read (pull_weights): keys [n] -> out [n, dim] fp32, one G-lane
+// group per key. Every lane of the group runs the same resolve (one
+// address per probe across the group), then the lanes dequantize the row's
+// dwords; a miss writes zeros.
+template <int FMT, int G, typename Resolve>
+__global__ void k_gather_lookup_q(const unsigned int* __restrict__ slab,
+                                  long dim, long n, float* __restrict__ out,
+                                  Resolve resolve) {
+    constexpr int CPD = QFmt<FMT>::CPD;
+    const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    const int lane = threadIdx.x % G;
+    if (i >= n) return;
+    const long row = resolve(i, n);
+    const long ndw = QFmt<FMT>::code_dwords(dim);
+    const unsigned int* __restrict__ r =
+        slab + (u64)(row >= 0 ? row : 0) * (QFmt<FMT>::stride(dim) / 4);
+    // unconditional loads (a miss reads row 0; never launched with R == 0),
+    // zeroed afterwards, so scale / lo and the codes are one round trip
+    float rs = 0.0f, rl = 0.0f;
+    if constexpr (FMT == QF_INT8) {
+        rs = __uint_as_float(r[ndw]);
+        rl = __uint_as_float(r[ndw + 1]);
+        if (row < 0) rs = rl = 0.0f;
+    }
+    for (long d = lane; d < ndw; d += G) {
+        float x[CPD];
+        const unsigned int word = r[d];
+        q_unpack<FMT>(row >= 0 ? word : 0u, rs, rl, x);
+        #pragma unroll
+        for (int k = 0; k < CPD; ++k) {
+            const long c = d * CPD + k;
+            if (c < dim) out[(u64)i * dim + c] = x[k];
+        }
+    }
+}
+
 // -------------------------------------------------------- reduce-by-inverse
 // Hot rows (small-vocab fields) make direct global atomics serialize; for
 // dim <= 32 gradients+counts are pre-aggregated in an LDS hash per block
@@ -1968,6 +2271,77 @@ static void pool_lookup_dispatch(const float* rows, long dim, long nnz,
 #undef LAUNCH_LOOKUP
 }
 
+// The group ladders of the packed kernels go by a row's dword count
+// (ceil(dim / 4) for int8, ceil(dim / 2) for fp16). The row-parallel
+// kernels (quantize, flat gather): 4 lanes up to 4 dwords (a dim-9 int8 row
+// is three), 16 up to 16, 32 up to 32, a wave above.
+#define Q_ROW_LADDER(ndw, LAUNCH)                                           \
+    do {                                                                    \
+        if ((ndw) <= 4) LAUNCH(4);                                          \
+        else if ((ndw) <= 16) LAUNCH(16);                                   \
+        else if ((ndw) <= 32) LAUNCH(32);                                   \
+        else LAUNCH(64);                                                    \
+    } while (0)
+
+template <int FMT>
+static void quantize_dispatch(const float* w, long n, long dim,
+                              const i64* slots, unsigned int* slab, long R,
+                              hipStream_t stream) {
+#define LAUNCH_QUANT(G)                                                     \
+    k_quantize_rows<FMT, G><<<grid1d(n * G), BLOCK, 0, stream>>>(           \
+        w, n, dim, slots, slab, R)
+    Q_ROW_LADDER(QFmt<FMT>::code_dwords(dim), LAUNCH_QUANT);
+#undef LAUNCH_QUANT
+}
+
+template <int FMT, bool WEIGHTED, typename Resolve>
+static void pool_lookup_q_dispatch(const unsigned int* slab, long dim,
+                                   long nnz, const i64* offsets, long B,
+                                   int mode, const float* weights, float* out,
+                                   const Resolve& resolve,
+                                   hipStream_t stream) {
+    if (B == 0) return;
+#define LAUNCH_LOOKUP_Q(G, CF, ILP)                                         \
+    k_pool_lookup_q<FMT, G, CF, ILP, WEIGHTED, Resolve>                     \
+        <<<grid1d(B * G), BLOCK, 0, stream>>>(slab, dim, nnz, offsets, B,   \
+                                              mode, weights, out, resolve)
+    // The pooled lookup: 16 lanes up to 16 dwords, 32 up to 32, a wave
+    // above, two fragments per lane from 65 dwords, wider rows loop. There
+    // is no 4-lane rung: a group probes G keys per dependent round, and
+    // a bag of 32 walked four keys at a time measured 88 us against 38 us
+    // for the fp32 lookup's 16 lanes (profiles/serving_quantized.md)
+    const long ndw = QFmt<FMT>::code_dwords(dim);
+    if (ndw <= 16) LAUNCH_LOOKUP_Q(16, 1, 8);
+    else if (ndw <= 32) LAUNCH_LOOKUP_Q(32, 1, 8);
+    else if (ndw <= 64) LAUNCH_LOOKUP_Q(64, 1, 8);
+    else LAUNCH_LOOKUP_Q(64, 2, 4);
+#undef LAUNCH_LOOKUP_Q
+}
+
+template <int FMT, typename Resolve>
+static void pool_lookup_q_fmt(const unsigned int* slab, long dim, long nnz,
+                              const i64* offsets, long B, int mode,
+                              const float* weights, float* out,
+                              const Resolve& resolve, hipStream_t stream) {
+    if (weights)
+        pool_lookup_q_dispatch<FMT, true>(slab, dim, nnz, offsets, B, mode,
+                                          weights, out, resolve, stream);
+    else
+        pool_lookup_q_dispatch<FMT, false>(slab, dim, nnz, offsets, B, mode,
+                                           nullptr, out, resolve, stream);
+}
+
+template <int FMT, typename Resolve>
+static void gather_lookup_q_fmt(const unsigned int* slab, long dim, long n,
+                                float* out, const Resolve& resolve,
+                                hipStream_t stream) {
+#define LAUNCH_GATHER_Q(G)                                                  \
+    k_gather_lookup_q<FMT, G, Resolve>                                      \
+        <<<grid1d(n * G), BLOCK, 0, stream>>>(slab, dim, n, out, resolve)
+    Q_ROW_LADDER(QFmt<FMT>::code_dwords(dim), LAUNCH_GATHER_Q);
+#undef LAUNCH_GATHER_Q
+}
+
 template <bool IDX>
 static void unique_launch(const i64* keys, long n, u64* tk, int* tv, long cap,
                           int* slot_of, unsigned char* is_first,
@@ -2163,6 +2537,82 @@ void emb_pool_lookup(const float* rows, long R, long dim, const i64* values,
         else
             pool_lookup_dispatch<false>(rows, dim, nnz, offsets, B, mode,
                                         nullptr, out, r, stream);
+    }
+}
+
+// ---- quantized serving tables
+long emb_quant_stride(int fmt, long dim) {
+    return fmt == QF_INT8 ? QFmt<QF_INT8>::stride(dim)
+                          : QFmt<QF_FP16>::stride(dim);
+}
+
+// fp32 rows w [n, dim] -> packed rows slots[i] of slab [R, stride(fmt, dim)]
+void emb_quantize_rows(int fmt, const float* w, long n, long dim,
+                       const i64* slots, void* slab, long R,
+                       hipStream_t stream) {
+    if (n == 0) return;
+    if (fmt == QF_INT8)
+        quantize_dispatch<QF_INT8>(w, n, dim, slots, (unsigned int*)slab, R,
+                                   stream);
+    else
+        quantize_dispatch<QF_FP16>(w, n, dim, slots, (unsigned int*)slab, R,
+                                   stream);
+}
+
+// read-only pooled lookup over a packed slab [R, stride(fmt, dim)]; the
+// table arguments are emb_pool_lookup's
+void emb_pool_lookup_q(int fmt, const void* slab, long R, long dim,
+                       const i64* values, long nnz, const i64* offsets,
+                       long B, int mode, const float* weights, const u64* tk,
+                       const int* tv, long cap, const unsigned char* valid,
+                       long shard_num, float* out, hipStream_t stream) {
+    if (R == 0) {   // nothing to read (the kernel reads row 0 for a miss)
+        fill_f32(out, B * dim, 0.0f, stream);
+        return;
+    }
+    const unsigned int* s = (const unsigned int*)slab;
+    if (tk) {
+        const PoolHashKeys r{values, tk, tv, cap - 1, R};
+        if (fmt == QF_INT8)
+            pool_lookup_q_fmt<QF_INT8>(s, dim, nnz, offsets, B, mode,
+                                       weights, out, r, stream);
+        else
+            pool_lookup_q_fmt<QF_FP16>(s, dim, nnz, offsets, B, mode,
+                                       weights, out, r, stream);
+    } else {
+        const PoolArrayKeys r{values, valid, shard_num, cap, R};
+        if (fmt == QF_INT8)
+            pool_lookup_q_fmt<QF_INT8>(s, dim, nnz, offsets, B, mode,
+                                       weights, out, r, stream);
+        else
+            pool_lookup_q_fmt<QF_FP16>(s, dim, nnz, offsets, B, mode,
+                                       weights, out, r, stream);
+    }
+}
+
+// flat read over a packed slab: keys [n] -> out [n, dim], zeros for a miss
+void emb_gather_lookup_q(int fmt, const void* slab, long R, long dim,
+                         const i64* keys, long n, const u64* tk,
+                         const int* tv, long cap, const unsigned char* valid,
+                         long shard_num, float* out, hipStream_t stream) {
+    if (n == 0) return;
+    if (R == 0) {   // nothing to read (the kernel reads row 0 for a miss)
+        fill_f32(out, n * dim, 0.0f, stream);
+        return;
+    }
+    const unsigned int* s = (const unsigned int*)slab;
+    if (tk) {
+        const PoolHashKeys r{keys, tk, tv, cap - 1, R};
+        if (fmt == QF_INT8)
+            gather_lookup_q_fmt<QF_INT8>(s, dim, n, out, r, stream);
+        else
+            gather_lookup_q_fmt<QF_FP16>(s, dim, n, out, r, stream);
+    } else {
+        const PoolArrayKeys r{keys, valid, shard_num, cap, R};
+        if (fmt == QF_INT8)
+            gather_lookup_q_fmt<QF_INT8>(s, dim, n, out, r, stream);
+        else
+            gather_lookup_q_fmt<QF_FP16>(s, dim, n, out, r, stream);
     }
 }
 

@@ -104,6 +104,17 @@ def reduce_by_index(index, grads: torch.Tensor, u_dev
 POOL_MODES = {"sum": 0, "mean": 1, "sqrtn": 2}
 
 
+def _sqrt(t: torch.Tensor) -> torch.Tensor:
+    """Correctly rounded square root, like the kernels' ``sqrtf``. torch's
+    float32 sqrt on the CPU is off by an ulp for about 0.7 % of inputs
+    (the bag length 267 is the first integer), which would make this
+    oracle differ from the kernels it defines; the float64 root of a
+    float32 rounds to the correct float32."""
+    if t.dtype == torch.float32:
+        return t.double().sqrt().to(torch.float32)
+    return t.sqrt()
+
+
 def _bag_scale(offsets: torch.Tensor, nnz: int, mode: str,
                dtype: torch.dtype) -> torch.Tensor:
     """Combiner scale per bag: 1 (sum), 1/len (mean), 1/sqrt(len) (sqrtn);
@@ -116,7 +127,7 @@ def _bag_scale(offsets: torch.Tensor, nnz: int, mode: str,
     elif mode == "mean":
         scale = 1.0 / length
     else:
-        scale = 1.0 / length.sqrt()
+        scale = 1.0 / _sqrt(length)
     return torch.where(length > 0, scale, torch.zeros_like(scale))
 
 
@@ -237,7 +248,7 @@ def _weighted_scale(weights: torch.Tensor, bag: torch.Tensor, B: int,
     den = den.index_add(0, bag.clamp(min=0), w if mode == "mean" else w * w)
     nz = den != 0
     safe = torch.where(nz, den, torch.ones_like(den))
-    scale = 1.0 / safe if mode == "mean" else 1.0 / safe.sqrt()
+    scale = 1.0 / safe if mode == "mean" else 1.0 / _sqrt(safe)
     return w, torch.where(nz, scale, torch.zeros_like(scale))
 
 
@@ -346,6 +357,122 @@ def pool_wgrad(rows: torch.Tensor, inverse, row_map, weights: torch.Tensor,
         c = 1.0 if mode == "mean" else weights.to(rows.dtype) * s
         dw = s * (gr - c * go)
     return torch.where(live, dw, torch.zeros_like(dw))
+
+
+# ------------------------------------------------ quantized serving tables
+
+QUANT_FORMATS = {"int8": 0, "fp16": 1}
+FP16_MAX = 65504.0
+_FLT_MIN = 1.1754943508222875e-38     # 2**-126, smallest normal float32
+
+
+def _check_fmt(fmt: str) -> None:
+    if fmt not in QUANT_FORMATS:
+        raise ValueError(f"unknown row format {fmt!r}; expected one of "
+                         f"{sorted(QUANT_FORMATS)}")
+
+
+def row_stride(fmt: str, dim: int) -> int:
+    """Bytes per packed row, a multiple of 4. int8: ``dim`` codes padded to
+    a dword, then fp32 scale and fp32 lo. fp16: ``dim`` halves padded to a
+    dword."""
+    _check_fmt(fmt)
+    if dim < 1:
+        raise ValueError("dim must be >= 1")
+    if fmt == "int8":
+        return 4 * ((dim + 3) // 4) + 8
+    return 4 * ((dim + 1) // 2)
+
+
+def quantize_problems(w: torch.Tensor, fmt: str):
+    """Why a block of fp32 rows cannot be stored in ``fmt``, or None: a
+    non-finite value, a non-finite ``max - min`` of a row (int8 needs the
+    span), or for fp16 a magnitude above 65504. Reads row minima and maxima
+    only — no [n, dim] temporary. One host sync; import-time use."""
+    _check_fmt(fmt)
+    if w.numel() == 0:
+        return None
+    lo = w.amin(dim=1)          # amin / amax propagate NaN
+    hi = w.amax(dim=1)
+    if not bool((torch.isfinite(lo) & torch.isfinite(hi)).all()):
+        return "a row holds a non-finite value"
+    if not bool(torch.isfinite(hi - lo).all()):
+        return "max - min of a row overflows float32"
+    if fmt == "fp16" and bool((torch.maximum(hi, -lo) > FP16_MAX).any()):
+        return f"a value exceeds the float16 range (|x| > {FP16_MAX:g})"
+    return None
+
+
+def quantize_rows(w: torch.Tensor, fmt: str) -> torch.Tensor:
+    """fp32 rows [n, dim] -> packed rows uint8 [n, row_stride(fmt, dim)].
+
+    int8, all in float32 and in this order: ``lo = min(row)`` (a -0.0
+    minimum is stored as +0.0), ``hi = max(row)``,
+    ``scale = (hi - lo) / 255``; a scale below FLT_MIN (zero or subnormal)
+    becomes 0 with every code 0, otherwise
+    ``code = clamp(rint((x - lo) / scale), 0, 255)`` (half to even).
+    fp16: round-to-nearest-even halves. Pad bytes are zero. Rows that
+    ``quantize_problems`` names raise ValueError. This torch form is the
+    CPU path and the oracle of ``k_quantize_rows``, which fills the same
+    bytes on a cuda tensor."""
+    _check_fmt(fmt)
+    if w.dim() != 2 or w.dtype != torch.float32:
+        raise ValueError("quantize_rows takes float32 [n, dim] rows")
+    bad = quantize_problems(w, fmt)
+    if bad is not None:
+        raise ValueError(f"cannot quantize to {fmt}: {bad}")
+    n, dim = w.shape
+    stride = row_stride(fmt, dim)
+    if _use_hip(w):
+        ext = require_hip()
+        if ext is not None:
+            slab = torch.empty((n, stride), dtype=torch.uint8,
+                               device=w.device)
+            ext.quantize_rows(w.contiguous(),
+                              torch.arange(n, device=w.device), slab,
+                              QUANT_FORMATS[fmt])
+            return slab
+    out = torch.zeros((n, stride), dtype=torch.uint8, device=w.device)
+    if n == 0:
+        return out
+    if fmt == "fp16":
+        out[:, :2 * dim] = w.to(torch.float16).contiguous() \
+            .view(torch.uint8).view(n, 2 * dim)
+        return out
+    lo = w.amin(dim=1) + 0.0
+    hi = w.amax(dim=1)
+    # a tensor divisor: every backend then does a true division, not a
+    # multiply by a rounded reciprocal
+    scale = (hi - lo) / torch.full_like(lo, 255.0)
+    live = scale >= _FLT_MIN
+    scale = torch.where(live, scale, torch.zeros_like(scale))
+    safe = torch.where(live, scale, torch.ones_like(scale))
+    q = torch.round((w - lo.unsqueeze(1)) / safe.unsqueeze(1)).clamp(0, 255)
+    q = torch.where(live.unsqueeze(1), q, torch.zeros_like(q))
+    cw = stride - 8
+    out[:, :dim] = q.to(torch.uint8)
+    out[:, cw:cw + 4] = scale.contiguous().view(torch.uint8).view(n, 4)
+    out[:, cw + 4:] = lo.contiguous().view(torch.uint8).view(n, 4)
+    return out
+
+
+def dequantize_rows(packed: torch.Tensor, dim: int, fmt: str) -> torch.Tensor:
+    """Packed rows uint8 [n, row_stride(fmt, dim)] -> fp32 [n, dim]:
+    ``lo + scale * float(code)`` (one multiply, then one add) for int8,
+    ``float(half)`` for fp16. Plain torch on every device — the oracle of
+    the dequantizing lookups, which never materialise this tensor."""
+    stride = row_stride(fmt, dim)
+    if packed.dim() != 2 or packed.dtype != torch.uint8 \
+            or packed.shape[1] != stride:
+        raise ValueError(f"packed rows must be uint8 [n, {stride}]")
+    n = packed.shape[0]
+    if fmt == "fp16":
+        return packed[:, :2 * dim].contiguous().view(torch.float16) \
+            .view(n, dim).float()
+    cw = stride - 8
+    scale = packed[:, cw:cw + 4].contiguous().view(torch.float32).view(n, 1)
+    lo = packed[:, cw + 4:].contiguous().view(torch.float32).view(n, 1)
+    return lo + scale * packed[:, :dim].float()
 
 
 # ----------------------------------------------------------------- fused loss

@@ -41,6 +41,38 @@ class ModelStatus:
     ERROR = "ERROR"
 
 
+STORAGE_KINDS = ("fp32", "int8", "fp16")
+
+
+def check_quantize(quantize: Optional[str]) -> Optional[str]:
+    """``quantize`` of a load: None (fp32 tables) or a packed row format."""
+    if quantize is None or quantize in STORAGE_KINDS[1:]:
+        return quantize
+    raise ValueError(f"quantize must be one of {list(STORAGE_KINDS[1:])} "
+                     f"or None, got {quantize!r}")
+
+
+def _make_shard(mvar: dict, device: str, quantize: Optional[str]):
+    """The read-only table of one variable of a dump's meta: an fp32
+    (Hip)VariableShard, or a QuantizedShard when ``quantize`` names a packed
+    row format (rows are then quantized block by block as they arrive; no
+    fp32 table is ever built)."""
+    vm = VariableMeta(variable_id=mvar["variable_id"],
+                      embedding_dim=mvar["embedding_dim"],
+                      vocabulary_size=mvar["vocabulary_size"])
+    if quantize is not None:
+        if mvar.get("datatype", "float32") != "float32":
+            raise ValueError(
+                f"variable {vm.variable_id} is {mvar['datatype']}: only "
+                "float32 variables can be served quantized")
+        from .core.quantized import QuantizedShard
+        return QuantizedShard(vm, quantize, device=device)
+    if device.startswith("cuda"):
+        from .core.variable_gpu import HipVariableShard
+        return HipVariableShard(vm, shard_id=0, shard_num=1, device=device)
+    return VariableShard(vm, shard_id=0, shard_num=1, device=device)
+
+
 class ServedVariable:
     """Read-only handle over one loaded variable (reference
     EmbeddingVariableHandle in read-only mode)."""
@@ -51,6 +83,29 @@ class ServedVariable:
     @property
     def embedding_dim(self) -> int:
         return self.shard.dim
+
+    @property
+    def storage(self) -> str:
+        """"fp32", or the packed row format of a quantized table."""
+        return getattr(self.shard, "fmt", "fp32")
+
+    @property
+    def table_bytes(self) -> int:
+        """Bytes the table holds, key map included: a quantized table's
+        packed slab, an fp32 table's allocated weight and state rows, plus
+        whichever of the probe table, the row -> key list and the valid
+        bitmap the shard keeps as tensors (the CPU hash shards index with a
+        dict, which is not counted)."""
+        sh = self.shard
+        if hasattr(sh, "nbytes"):
+            return int(sh.nbytes)
+        total = 0
+        for name in ("weights", "state", "tk", "tv", "slot_keys",
+                     "valid_u8", "valid"):
+            t = getattr(sh, name, None)
+            if torch.is_tensor(t):
+                total += t.numel() * t.element_size()
+        return int(total)
 
     def pull_weights(self, indices: torch.Tensor) -> torch.Tensor:
         flat = indices.reshape(-1).to(torch.int64).to(self.shard.device)
@@ -124,31 +179,35 @@ class ServedModel:
         self.variables: Dict[int, ServedVariable] = {}
         self.meta: Optional[dict] = None
 
-    def load(self, device: str = "cpu") -> None:
+    def load(self, device: str = "cpu",
+             quantize: Optional[str] = None) -> None:
         """Stream the dump into read-only tables. All shards of the dump are
         merged into one local table (shard_num=1 view — serving is per-key
         lookup, the training shard layout is irrelevant).
 
         On a cuda device the tables are HipVariableShards, so serving pulls
         run the same k_ht_lookup / k_gather_init HIP kernels as training
-        (the round-1 CPU-table fallback bypassed every kernel)."""
+        (the round-1 CPU-table fallback bypassed every kernel).
+
+        ``quantize`` = "int8" | "fp16" builds QuantizedShards instead: every
+        block is quantized into a packed slab as it is read, and the slab is
+        reserved from the row counts in the dump's section headers."""
+        quantize = check_quantize(quantize)
         meta = read_meta(self.uri)
         self.meta = meta
-        shard_cls = VariableShard
-        if device.startswith("cuda"):
-            from .core.variable_gpu import HipVariableShard
-            shard_cls = HipVariableShard
+        self.quantize = quantize
         shards: Dict[int, VariableShard] = {}
         for mvar in meta["variables"]:
-            vm = VariableMeta(variable_id=mvar["variable_id"],
-                              embedding_dim=mvar["embedding_dim"],
-                              vocabulary_size=mvar["vocabulary_size"])
-            shards[vm.variable_id] = shard_cls(vm, shard_id=0, shard_num=1,
-                                               device=device)
+            shards[mvar["variable_id"]] = _make_shard(mvar, device, quantize)
+        section = None
         for hdr, keys, w, _s in iter_blocks(self.uri, meta):
             sh = shards.get(hdr["variable_id"])
             if sh is None or not len(keys):
                 continue
+            if quantize is not None and hdr is not section:
+                section = hdr       # one header per (file, variable) section
+                if "num_items" in hdr:
+                    sh.reserve_rows(sh.num_rows + int(hdr["num_items"]))
             # frombuffer arrays are read-only; copy before wrapping (torch
             # tensors over read-only memory are undefined behavior)
             kt = torch.from_numpy(keys.copy())
@@ -181,32 +240,34 @@ class ServedModel:
 
     def load_from_replica(self, base_url: str, sign: str,
                           device: str = "cpu",
-                          block: int = 65536) -> None:
+                          block: int = 65536,
+                          quantize: Optional[str] = None) -> None:
         """Coordinated restore: rebuild this model's tables by paging rows
         out of a LIVE replica (no dump needed — the reference's
-        restore-from-replica path for a replacement server)."""
+        restore-from-replica path for a replacement server). With
+        ``quantize`` the pages are quantized as they arrive; pages of a
+        replica that is itself quantized are dequantized rows, so
+        re-quantizing them is lossy once more (docs/serving.md)."""
         import requests
+
+        quantize = check_quantize(quantize)
+        self.quantize = quantize
 
         meta = requests.get(f"{base_url}/models/{sign}", timeout=10).json()
         self.meta = {"model_sign": meta["model_sign"],
                      "variables": meta["variables"], "version": "0.2"}
-        shard_cls = VariableShard
-        if device.startswith("cuda"):
-            from .core.variable_gpu import HipVariableShard
-            shard_cls = HipVariableShard
         shards: Dict[int, VariableShard] = {}
         for mvar in meta["variables"]:
-            vm = VariableMeta(variable_id=mvar["variable_id"],
-                              embedding_dim=mvar["embedding_dim"],
-                              vocabulary_size=mvar["vocabulary_size"])
-            sh = shard_cls(vm, shard_id=0, shard_num=1, device=device)
+            sh = _make_shard(mvar, device, quantize)
+            vid = mvar["variable_id"]
             start = 0
             while True:
                 r = requests.get(
-                    f"{base_url}/models/{sign}/variables/"
-                    f"{vm.variable_id}/rows",
+                    f"{base_url}/models/{sign}/variables/{vid}/rows",
                     params={"start": start, "count": block},
                     timeout=60).json()
+                if quantize is not None and start == 0:
+                    sh.reserve_rows(int(r["total"]))
                 if r["keys"]:
                     kt = torch.tensor(r["keys"], dtype=torch.int64,
                                       device=sh.device)
@@ -216,7 +277,7 @@ class ServedModel:
                 start += block
                 if start >= r["total"]:
                     break
-            shards[vm.variable_id] = sh
+            shards[vid] = sh
         self.variables = {vid: ServedVariable(sh)
                           for vid, sh in shards.items()}
         self.status = ModelStatus.NORMAL
@@ -230,9 +291,20 @@ class ServedModel:
             "variables": ([
                 {"variable_id": v["variable_id"],
                  "embedding_dim": v["embedding_dim"],
-                 "vocabulary_size": v["vocabulary_size"]}
+                 "vocabulary_size": v["vocabulary_size"],
+                 **self._storage_of(v["variable_id"])}
                 for v in self.meta["variables"]] if self.meta else []),
         }
+
+    def _storage_of(self, variable_id: int) -> dict:
+        """``storage`` ("fp32" | "int8" | "fp16") and ``table_bytes`` of a
+        variable; while the model is still loading, the storage it was
+        asked for and 0 bytes."""
+        var = self.variables.get(variable_id)
+        if var is None:
+            return {"storage": getattr(self, "quantize", None) or "fp32",
+                    "table_bytes": 0}
+        return {"storage": var.storage, "table_bytes": var.table_bytes}
 
 
 class ModelManager:
@@ -282,10 +354,14 @@ class ModelController:
         self.shutdown_requested = False
 
     def create_model(self, model_uri: str, sign: Optional[str] = None,
-                     wait: bool = True) -> ServedModel:
+                     wait: bool = True,
+                     quantize: Optional[str] = None) -> ServedModel:
         """Load a dump for serving. sign defaults to the dump's model_sign.
         wait=False returns immediately with status CREATING (reference async
-        heavy load, ModelController.cpp:66-82)."""
+        heavy load, ModelController.cpp:66-82). ``quantize`` = "int8" |
+        "fp16" serves from packed tables (ServedModel.load); an unknown
+        value raises ValueError before anything is registered."""
+        quantize = check_quantize(quantize)
         meta = read_meta(model_uri)
         sign = sign or meta["model_sign"]
         existing = self.manager.get(sign)
@@ -296,7 +372,7 @@ class ModelController:
 
         def _load():
             try:
-                model.load(device=self.manager.device)
+                model.load(device=self.manager.device, quantize=quantize)
             except Exception as e:  # noqa: BLE001
                 model.status = ModelStatus.ERROR
                 model.error = repr(e)
@@ -311,10 +387,13 @@ class ModelController:
         return model
 
     def restore_model_from_replica(self, base_url: str, sign: str,
-                                   wait: bool = True) -> ServedModel:
+                                   wait: bool = True,
+                                   quantize: Optional[str] = None
+                                   ) -> ServedModel:
         """Coordinated restore from a live replica (reference
         EmbeddingRestoreOperator replica path / server --restore): page
         the rows out of ``base_url`` instead of a dump URI."""
+        quantize = check_quantize(quantize)
         existing = self.manager.get(sign)
         if existing is not None and existing.status != ModelStatus.ERROR:
             raise ValueError(f"model {sign!r} already exists")
@@ -324,7 +403,8 @@ class ModelController:
         def _load():
             try:
                 model.load_from_replica(base_url, sign,
-                                        device=self.manager.device)
+                                        device=self.manager.device,
+                                        quantize=quantize)
             except Exception as e:  # noqa: BLE001
                 model.status = ModelStatus.ERROR
                 model.error = repr(e)
@@ -436,11 +516,22 @@ class ServingClient:
     def show_models(self) -> List[dict]:
         return self._request("GET", "/models")
 
+    def create_model(self, model_uri: str, sign: Optional[str] = None,
+                     quantize: Optional[str] = None) -> dict:
+        """``POST /models`` on one replica (the next in rotation)."""
+        body = {"model_uri": model_uri}
+        if sign is not None:
+            body["sign"] = sign
+        if quantize is not None:
+            body["quantize"] = quantize
+        return self._request("POST", "/models", body)
+
 
 def make_app(controller: Optional[ModelController] = None,
              device: str = "cpu"):
     """REST surface (reference entry/controller.cc routes):
-      POST   /models            {"model_uri": ..., "sign"?: ..., "wait"?: bool}
+      POST   /models            {"model_uri": ..., "sign"?: ..., "wait"?: bool,
+                                 "quantize"?: "int8"|"fp16"}
       GET    /models            list
       GET    /models/{sign}     describe
       DELETE /models/{sign}
@@ -469,6 +560,8 @@ def make_app(controller: Optional[ModelController] = None,
         # coordinated restore: rebuild from a live replica instead of a
         # dump (requires sign; reference server --restore semantics)
         from_replica: Optional[str] = None
+        # serve from packed tables: "int8" | "fp16" (anything else: 422)
+        quantize: Optional[str] = None
 
     class PullReq(BaseModel):
         indices: list
@@ -482,18 +575,24 @@ def make_app(controller: Optional[ModelController] = None,
     @app.post("/models")
     def create_model(req: CreateModelReq):
         try:
+            check_quantize(req.quantize)
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        try:
             if req.from_replica:
                 if not req.sign:
                     raise HTTPException(status_code=422,
                                         detail="from_replica needs sign")
                 m = controller.restore_model_from_replica(
-                    req.from_replica, req.sign, wait=req.wait)
+                    req.from_replica, req.sign, wait=req.wait,
+                    quantize=req.quantize)
             else:
                 if not req.model_uri:
                     raise HTTPException(status_code=422,
                                         detail="model_uri required")
                 m = controller.create_model(req.model_uri, sign=req.sign,
-                                            wait=req.wait)
+                                            wait=req.wait,
+                                            quantize=req.quantize)
         except ValueError as e:
             raise HTTPException(status_code=409, detail=str(e))
         except (FileNotFoundError, RuntimeError) as e:
@@ -601,10 +700,13 @@ def main():  # pragma: no cover - thin CLI (reference controller daemon)
         "cuda:0" if torch.cuda.is_available() else "cpu"))
     p.add_argument("--model-uri", action="append", default=[],
                    help="dump URI(s) to load at startup")
+    p.add_argument("--quantize", choices=list(STORAGE_KINDS[1:]),
+                   default=None,
+                   help="serve the startup models from packed tables")
     args = p.parse_args()
     controller = ModelController(device=args.device)
     for uri in args.model_uri:
-        controller.create_model(uri)
+        controller.create_model(uri, quantize=args.quantize)
     uvicorn.run(make_app(controller), host=args.host, port=args.port)
 
 
