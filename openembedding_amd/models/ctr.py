@@ -377,18 +377,29 @@ class _CINLayerFn(torch.autograd.Function):
                 and n % 32 == 0)
 
     @staticmethod
+    def _wt_rows(F, H):
+        # k_cin_dx loads a whole 16-row Wt fragment for every h-tile of
+        # every field, so the last field's partial tile reads rows up to
+        # (F-1)*H + ceil16(H) - 1 — past ceil32(F*H) for e.g. F = H = 8
+        # (rows to 71 of 64). The rows are zero padding whose products the
+        # kernel discards; cin_dx requires exactly this many.
+        return (max(F * H, (F - 1) * H + (H + 15) // 16 * 16) + 31) // 32 * 32
+
+    @staticmethod
     def _bufs(W, F, H):
         # padded bf16 weight mirrors, cached on the parameter and
         # refreshed (copy_) every forward — same pattern as the fused MLP
         O, K = W.shape
         Kp = (K + 31) // 32 * 32
         Op = (O + 31) // 32 * 32
+        rows = _CINLayerFn._wt_rows(F, H)
         bufs = getattr(W, "_cin_bufs", None)
-        if bufs is None or bufs["wp"].shape != (O, Kp):
+        if (bufs is None or bufs["wp"].shape != (O, Kp)
+                or bufs["wt"].shape != (rows, Op)):
             bufs = {
                 "wp": torch.zeros(O, Kp, dtype=torch.bfloat16,
                                   device=W.device),
-                "wt": torch.zeros(Kp, Op, dtype=torch.bfloat16,
+                "wt": torch.zeros(rows, Op, dtype=torch.bfloat16,
                                   device=W.device),
             }
             W._cin_bufs = bufs

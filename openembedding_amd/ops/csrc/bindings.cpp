@@ -1211,8 +1211,9 @@ torch::Tensor cin_fwd(torch::Tensor x0p, torch::Tensor xkp,
     const c10::cuda::CUDAGuard guard(x0p.device());
     long N = x0p.size(0), F = x0p.size(1), H = xkp.size(1);
     long O = wp.size(0), Kp = wp.size(1);
-    TORCH_CHECK(F <= 32 && H <= 128 && O <= 128 && O % 16 == 0
-                && Kp % 32 == 0 && xkp.size(0) == N, "cin_fwd shapes");
+    TORCH_CHECK(F <= 32 && H <= 128 && O >= 16 && O <= 128 && O % 16 == 0
+                && Kp % 32 == 0 && Kp >= F * H && xkp.size(0) == N,
+                "cin_fwd shapes");
     auto out = torch::empty({N, O}, x0p.options());
     emb_cin_fwd(x0p.data_ptr<float>(), xkp.data_ptr<float>(), wp.data_ptr(),
                 out.data_ptr<float>(), N, F, H, O, Kp, cur_stream());
@@ -1227,8 +1228,11 @@ torch::Tensor cin_dw(torch::Tensor dzt, torch::Tensor x0t,
                 && xkt.dtype() == torch::kBFloat16, "cin_dw dtypes");
     const c10::cuda::CUDAGuard guard(dzt.device());
     long Np = dzt.size(1), F = x0t.size(0), H = xkt.size(0);
+    // each wave reads a full 16-row dZt fragment: an O that is no multiple
+    // of 16, or a dzt with fewer rows than O, would read past its end
     TORCH_CHECK(Np % 32 == 0 && x0t.size(1) == Np && xkt.size(1) == Np
-                && H <= 128 && O <= 128, "cin_dw shapes");
+                && F <= 32 && H <= 128 && O <= 128 && O % 16 == 0
+                && dzt.size(0) == O && n_split >= 1, "cin_dw shapes");
     auto dw = torch::zeros({O, F * H},
                            dzt.options().dtype(torch::kFloat32));
     emb_cin_dw(dzt.data_ptr(), x0t.data_ptr(), xkt.data_ptr(),
@@ -1242,12 +1246,24 @@ std::tuple<torch::Tensor, torch::Tensor> cin_dx(
     CHECK_GPU(doutp); CHECK_CONT(doutp); CHECK_CONT(wt); CHECK_CONT(x0p);
     CHECK_CONT(xkp);
     TORCH_CHECK(doutp.dtype() == torch::kFloat32
-                && wt.dtype() == torch::kBFloat16, "cin_dx dtypes");
+                && wt.dtype() == torch::kBFloat16
+                && x0p.dtype() == torch::kFloat32
+                && xkp.dtype() == torch::kFloat32, "cin_dx dtypes");
     const c10::cuda::CUDAGuard guard(doutp.device());
     long N = doutp.size(0), O = doutp.size(1);
     long F = x0p.size(1), H = xkp.size(1), Op = wt.size(1);
-    TORCH_CHECK(Op % 32 == 0 && O <= Op && F <= 32 && H <= 128
-                && wt.size(0) >= F * H, "cin_dx shapes");
+    // k_cin_dx loads a whole 16-row Wt fragment per h-tile, so the last
+    // field's partial tile reads rows up to (F-1)*H + ceil16(H) - 1; wt
+    // carries zero rows up to there (padded, not bounds-checked: a check
+    // in the fragment loader scalarizes the k-loop, docs/hacking.md).
+    // The LDS dZ tile is 128 wide, hence Op <= 128.
+    long rows = F * H > (F - 1) * H + (H + 15) / 16 * 16
+                    ? F * H : (F - 1) * H + (H + 15) / 16 * 16;
+    rows = (rows + 31) / 32 * 32;
+    TORCH_CHECK(Op % 32 == 0 && Op <= 128 && O >= 1 && O <= Op
+                && F >= 1 && F <= 32 && H <= 128
+                && x0p.size(0) == N && xkp.size(0) == N
+                && wt.size(0) == rows, "cin_dx shapes");
     auto dx0 = torch::empty({N, F}, x0p.options());
     auto dxk = torch::empty({N, H}, xkp.options());
     emb_cin_dx(doutp.data_ptr<float>(), wt.data_ptr(),

@@ -267,8 +267,11 @@ extern "C" void emb_cin_dw(const void* dzt, const void* x0t, const void* xkt,
 // LDS staging tile, and the consume phase is plain bank-padded LDS
 // arithmetic — NO atomics (the first version accumulated through LDS
 // float atomics and measured 1.2 ms/call: contention turns them into
-// serialized CAS traffic). Wt [Kp, Op] is the bf16 transposed weight copy;
-// block = 64 columns.
+// serialized CAS traffic). Wt [rows, Op] is the bf16 transposed weight copy;
+// block = 64 columns. A whole 16-row Wt fragment is loaded for every h-tile
+// of every field, so the last field's partial tile reads rows up to
+// (F-1)*H + ceil16(H) - 1: rows = ceil32 of that, zero padded (the binding
+// requires it), and the h < H guard on the P store discards those rows.
 
 #define CDX_COLS 64
 #define CDX_X0LD 36     // x0/dx0 LDS row stride (bank-cycling pad)
@@ -277,7 +280,7 @@ extern "C" void emb_cin_dw(const void* dzt, const void* x0t, const void* xkt,
 
 extern "C" __global__ __launch_bounds__(64 * CIN_WAVES, 1)
 void k_cin_dx(const float* __restrict__ doutp,  // [N, O] fp32
-              const cbf16* __restrict__ wt,     // [Kp, Op]
+              const cbf16* __restrict__ wt,     // [rows, Op], see above
               const float* __restrict__ x0p,    // [N, F]
               const float* __restrict__ xkp,    // [N, H]
               float* __restrict__ dx0p,         // [N, F] out

@@ -14,6 +14,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from openembedding_amd.models.ctr import _CINLayerFn  # noqa: E402
 from openembedding_amd.ops import require_hip  # noqa: E402
 
 DEV = "cuda:0"
@@ -21,13 +22,14 @@ ext = require_hip()
 bf = torch.bfloat16
 
 
-def pad_w(W, Kp, Op=None):
+def pad_w(W, Kp, Op=None, F=None, H=None):
     O, K = W.shape
     wp = torch.zeros(O, Kp, dtype=bf, device=DEV)
     wp[:, :K] = W
     if Op is None:
         return wp
-    wt = torch.zeros(Kp, Op, dtype=bf, device=DEV)
+    # cin_dx wants the rows its last 16-row fragment reads, not ceil32(K)
+    wt = torch.zeros(_CINLayerFn._wt_rows(F, H), Op, dtype=bf, device=DEV)
     wt[:K, :O] = W.t()
     return wp, wt
 
@@ -61,7 +63,7 @@ def main():
         x0p = torch.randn(N, F, device=DEV)
         xkp = torch.randn(N, H, device=DEV)
         W = (torch.randn(O, K, device=DEV) * 0.05)
-        wp, wt = pad_w(W, Kp, Op)
+        wp, wt = pad_w(W, Kp, Op, F, H)
         wbf = wp[:, :K].float()
 
         # one-hot W: out[n][o] = V[n][o*step]

@@ -23,6 +23,18 @@ def _layer_io(B=512, F=26, H=128, O=128, d=9, seed=0):
 
 def _run(x0, xk, W, dout, force_torch):
     from openembedding_amd.models.ctr import _CINLayerFn
+    from openembedding_amd.ops import require_hip
+    ext = require_hip()
+    calls = []
+    real = {n: getattr(ext, n) for n in ("cin_fwd", "cin_dx", "cin_dw")}
+
+    def counted(name):
+        def wrapper(*a):
+            calls.append(name)
+            return real[name](*a)
+        return wrapper
+    for name in real:
+        setattr(ext, name, counted(name))
     x0 = x0.clone().requires_grad_(True)
     xk = xk.clone().requires_grad_(True)
     W = W.clone().requires_grad_(True)
@@ -35,6 +47,12 @@ def _run(x0, xk, W, dout, force_torch):
     finally:
         if force_torch:
             _CINLayerFn._hip_ok = orig
+        for name, fn in real.items():
+            setattr(ext, name, fn)
+    # the HIP path was taken exactly when it was meant to be: without this
+    # a False _hip_ok would compare the torch path with itself
+    assert sorted(calls) == ([] if force_torch
+                             else ["cin_dw", "cin_dx", "cin_fwd"]), calls
     return out.detach(), x0.grad, xk.grad, W.grad
 
 
@@ -50,8 +68,9 @@ def test_cin_kernels_match_torch(shape):
     # operands agree to bf16; the torch path additionally ROUNDS ITS
     # OUTPUTS to bf16 (library GEMM out dtype) while the kernels keep
     # fp32 accumulators, so the comparison tolerance is bf16-output-sized.
-    # scripts/diag_cin.py holds the kernels to tight exact-operand fp32
-    # references; this test pins end-to-end agreement of the two paths.
+    # tests/test_gpu_cin_kernels.py holds the kernels to an exact oracle
+    # (integer equality, derived fp32 bound) through their entry points;
+    # this test pins end-to-end agreement of the two paths.
     torch.testing.assert_close(out_h, out_t, rtol=8e-2, atol=8e-2)
     torch.testing.assert_close(dx0_h, dx0_t, rtol=8e-2, atol=8e-2)
     torch.testing.assert_close(dxk_h, dxk_t, rtol=8e-2, atol=8e-2)
