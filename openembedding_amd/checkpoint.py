@@ -20,6 +20,15 @@ Differences from the reference, by design:
 
 Every rank writes its own shard file (collective dump); load is collective,
 each rank reads all files and keeps its own keys.
+
+Delta checkpoints (no reference file format; the reference's incremental
+checkpoint was its PMem PersistManager): with change tracking on
+(``shard.track_changes``), ``dump_delta`` writes, in the same layout and
+section format, only the rows changed since an epoch, and ``apply_delta``
+upserts them on top of a loaded base. The meta of a tracked full dump gains
+``epoch`` and ``model_uuid``; a delta's meta gains
+``"delta": {since, epoch, model_uuid}`` and its section headers
+``"delta": true``. Rows are never deleted, so deltas hold upserts only.
 """
 
 from __future__ import annotations
@@ -55,14 +64,79 @@ def _var_header(var, include_optimizer: bool) -> dict:
     }
 
 
+def _shards(ctx):
+    return [var.shard for st in ctx.storages for var in st.variables]
+
+
+def tracked_epoch(ctx) -> Optional[int]:
+    """The change-tracking epoch of a context: None when no variable is
+    tracked; otherwise every variable must be, all at the same epoch (they
+    advance together, at every dump)."""
+    shards = _shards(ctx)
+    on = [sh for sh in shards if getattr(sh, "tracking", False)]
+    if not on:
+        return None
+    if len(on) != len(shards):
+        raise RuntimeError("change tracking is on for some variables only; "
+                           "track all of them or none")
+    epochs = {sh.epoch for sh in on}
+    if len(epochs) != 1:
+        raise RuntimeError(f"tracked variables disagree on the epoch: "
+                           f"{sorted(epochs)}")
+    return epochs.pop()
+
+
+def _advance(ctx, epoch: int, reset: bool = False) -> None:
+    for sh in _shards(ctx):
+        if getattr(sh, "tracking", False):
+            sh.set_epoch(epoch, reset=reset)
+
+
 def dump_model(ctx, uri: str, include_optimizer: bool = True) -> None:
-    """Collective: every rank writes its shard of every storage."""
-    rank, world = ctx.rank, ctx.world_size
+    """Collective: every rank writes its shard of every storage. With
+    change tracking on, the meta also records the dump's ``epoch`` and the
+    ``model_uuid`` (the base of a delta chain), and the epoch advances."""
+    meta = _model_meta(ctx)
+    epoch = tracked_epoch(ctx)
+    if epoch is not None:
+        meta["epoch"] = epoch
+        meta["model_uuid"] = ctx.model_uuid
+    _write_dump(ctx, uri, meta, include_optimizer, None)
+    if epoch is not None:
+        _advance(ctx, epoch + 1)
+
+
+def dump_delta(ctx, uri: str, include_optimizer: bool = True,
+               since: Optional[int] = None) -> dict:
+    """Collective: write only the rows changed since epoch ``since`` (default:
+    since the last dump of either kind, which chains the deltas; an explicit
+    earlier ``since`` serves a consumer that is further behind). Same layout
+    and shard-file format as ``dump_model``, so ``iter_blocks`` reads it;
+    the meta carries ``"delta": {since, epoch, model_uuid}``. Rows are never
+    deleted from a table, so a delta holds upserts only. Returns
+    ``{"since", "epoch", "rows"}`` (rows of this rank)."""
+    epoch = tracked_epoch(ctx)
+    if epoch is None:
+        raise RuntimeError("dump_delta needs change tracking: call "
+                           "track_server_model_changes() (or set "
+                           "server.track_changes) before training")
+    since = epoch if since is None else int(since)
+    if since < 1 or since > epoch:
+        raise ValueError(f"since must be in [1, {epoch}], got {since}")
+    meta = _model_meta(ctx)
+    meta["delta"] = {"since": since, "epoch": epoch,
+                     "model_uuid": ctx.model_uuid}
+    rows = _write_dump(ctx, uri, meta, include_optimizer, since)
+    _advance(ctx, epoch + 1)
+    return {"since": since, "epoch": epoch, "rows": rows}
+
+
+def _model_meta(ctx) -> dict:
     meta = {
         "model_sign": f"{ctx.model_uuid}-{ctx.model_version}",
         "version": "0.2",
         "num_storages": len(ctx.storages),
-        "world_size": world,
+        "world_size": ctx.world_size,
         "variables": [],
     }
     for st in ctx.storages:
@@ -79,6 +153,15 @@ def dump_model(ctx, uri: str, include_optimizer: bool = True) -> None:
                 "embedding_dim": var.shard.dim,
                 "vocabulary_size": var.shard.meta.vocabulary_size,
             })
+    return meta
+
+
+def _write_dump(ctx, uri: str, meta: dict, include_optimizer: bool,
+                since: Optional[int]) -> int:
+    """The files of a full dump (``since`` None) or of a delta; returns the
+    number of rows this rank wrote."""
+    rank = ctx.rank
+    rows = 0
     if rank == 0:
         os.makedirs(uri, exist_ok=True)
         for st in ctx.storages:
@@ -98,21 +181,56 @@ def dump_model(ctx, uri: str, include_optimizer: bool = True) -> None:
                  for i in range(n_files)]
         try:
             for j, var in enumerate(st.variables):
-                _dump_variable(files[j % n_files], var, include_optimizer)
+                if since is None:
+                    rows += _dump_variable(files[j % n_files], var,
+                                           include_optimizer)
+                else:
+                    rows += _dump_variable_delta(files[j % n_files], var,
+                                                 include_optimizer, since)
         finally:
             for f in files:
                 f.close()
     ctx.barrier()
+    return rows
 
 
-def _dump_variable(f, var, include_optimizer: bool) -> None:
-    keys, w, s = var.shard.export_rows(include_state=include_optimizer)
-    hdr = _var_header(var, include_optimizer and s is not None)
-    hdr["num_items"] = int(keys.numel())
+def _write_header(f, hdr: dict) -> None:
     hjson = json.dumps(hdr).encode()
     f.write(MAGIC)
     f.write(struct.pack("<q", len(hjson)))
     f.write(hjson)
+
+
+def _dump_variable_delta(f, var, include_optimizer: bool, since: int) -> int:
+    """One variable's section of a delta: the full-dump section format with
+    ``"delta": true`` in the header, rows streamed block by block from
+    ``export_changed`` (never a copy of the table)."""
+    shard = var.shard
+    want_state = bool(include_optimizer and shard.state_dim)
+    sel = shard.select_changed(since)
+    n = int(sel[1])   # the one host read of the changed-row count
+    hdr = _var_header(var, want_state)
+    hdr["num_items"] = n
+    hdr["delta"] = True
+    _write_header(f, hdr)
+    for keys, w, s in shard.export_changed(since, include_state=want_state,
+                                           selection=(sel[0], n)):
+        f.write(struct.pack("<q", int(keys.numel())))
+        f.write(keys.cpu().numpy().astype("<i8").tobytes())
+        f.write(w.cpu().numpy().astype("<f4").tobytes())
+        if want_state:
+            f.write(s.cpu().numpy().astype("<f4").tobytes())
+    if n == 0:
+        f.write(struct.pack("<q", 0))
+    f.write(struct.pack("<q", -1))  # end of variable section
+    return n
+
+
+def _dump_variable(f, var, include_optimizer: bool) -> int:
+    keys, w, s = var.shard.export_rows(include_state=include_optimizer)
+    hdr = _var_header(var, include_optimizer and s is not None)
+    hdr["num_items"] = int(keys.numel())
+    _write_header(f, hdr)
     n = keys.numel()
     sd = hdr["state_dim"]
     for start in range(0, max(n, 1), BLOCK_ROWS):
@@ -127,6 +245,7 @@ def _dump_variable(f, var, include_optimizer: bool) -> None:
         if sd:
             f.write(s[start:stop].cpu().numpy().astype("<f4").tobytes())
     f.write(struct.pack("<q", -1))  # end of variable section
+    return int(n)
 
 
 def _apply_config(var, hdr: dict) -> None:
@@ -194,8 +313,75 @@ def iter_blocks(uri: str, meta: Optional[dict] = None):
 def load_model(ctx, uri: str) -> None:
     """Collective: clears all variables, streams every shard file and keeps
     the keys this rank owns (key % world == rank), re-sharding like the
-    reference's load-through-init-push (EmbeddingLoadOperator.cpp:58-111)."""
+    reference's load-through-init-push (EmbeddingLoadOperator.cpp:58-111).
+
+    A delta directory is refused (loading clears the tables; use
+    ``apply_delta``). The context remembers the dump's ``epoch`` and
+    ``model_uuid`` as the base of a delta chain; a tracking context forgets
+    its stamps and continues at ``epoch + 1`` under the dump's uuid, so the
+    base is not re-emitted by its next delta."""
     meta = read_meta(uri)
+    if "delta" in meta:
+        raise RuntimeError(f"{uri} is a delta checkpoint: load its base "
+                           "with load_model, then apply_delta")
+    by_id = _match_variables(ctx, meta)
+    for mvar in meta["variables"]:
+        by_id[mvar["variable_id"]].shard.clear()
+    _import_blocks(ctx, uri, meta, by_id)
+    ctx.loaded_epoch = meta.get("epoch")
+    ctx.loaded_model_uuid = meta.get("model_uuid")
+    if tracked_epoch(ctx) is not None:
+        if ctx.loaded_epoch is not None:
+            ctx.model_uuid = ctx.loaded_model_uuid
+            _advance(ctx, ctx.loaded_epoch + 1, reset=True)
+        else:
+            _advance(ctx, tracked_epoch(ctx), reset=True)
+    ctx.barrier()
+
+
+def check_delta(meta: dict, loaded_uuid, loaded_epoch) -> dict:
+    """The ``delta`` record of a delta's meta if it applies on top of a model
+    loaded at ``loaded_epoch`` from ``loaded_uuid``; RuntimeError otherwise
+    (not a delta, another model, a gap in the chain, or already applied)."""
+    d = meta.get("delta")
+    if d is None:
+        raise RuntimeError("not a delta checkpoint (its meta has no "
+                           "\"delta\" record)")
+    if loaded_epoch is None or loaded_uuid is None:
+        raise RuntimeError("no delta-capable base is loaded: load a full "
+                           "dump written with change tracking on first")
+    if d["model_uuid"] != loaded_uuid:
+        raise RuntimeError(f"delta belongs to model {d['model_uuid']}, "
+                           f"loaded is {loaded_uuid}")
+    if d["since"] > loaded_epoch + 1:
+        raise RuntimeError(f"delta starts at epoch {d['since']} but the "
+                           f"loaded model is at {loaded_epoch}: an earlier "
+                           "delta is missing")
+    if d["epoch"] <= loaded_epoch:
+        raise RuntimeError(f"delta of epoch {d['epoch']} is already "
+                           f"contained in the loaded epoch {loaded_epoch}")
+    return d
+
+
+def apply_delta(ctx, uri: str) -> dict:
+    """Collective: upsert a delta's rows into the loaded tables (nothing is
+    cleared), re-sharded by key % world like ``load_model``. Refused with
+    RuntimeError, before anything changes, unless ``check_delta`` passes.
+    Afterwards ``ctx.loaded_epoch`` is the delta's epoch."""
+    meta = read_meta(uri)
+    d = check_delta(meta, getattr(ctx, "loaded_model_uuid", None),
+                    getattr(ctx, "loaded_epoch", None))
+    by_id = _match_variables(ctx, meta)
+    _import_blocks(ctx, uri, meta, by_id)
+    ctx.loaded_epoch = d["epoch"]
+    epoch = tracked_epoch(ctx)
+    if epoch is not None and epoch <= d["epoch"]:
+        _advance(ctx, d["epoch"] + 1)
+    ctx.barrier()
+    return d
+
+
+def _match_variables(ctx, meta: dict) -> dict:
     by_id = {}
     for st in ctx.storages:
         for var in st.variables:
@@ -208,7 +394,10 @@ def load_model(ctx, uri: str) -> None:
         if v.shard.dim != mvar["embedding_dim"]:
             raise RuntimeError(f"variable {vid}: dim mismatch "
                                f"{v.shard.dim} != {mvar['embedding_dim']}")
-        v.shard.clear()
+    return by_id
+
+
+def _import_blocks(ctx, uri: str, meta: dict, by_id: dict) -> None:
     rank, world = ctx.rank, ctx.world_size
     configured = set()
     for hdr, keys, w, s in iter_blocks(uri, meta):
@@ -228,4 +417,3 @@ def load_model(ctx, uri: str) -> None:
         if s is not None and sd == var.shard.state_dim:
             st_t = torch.from_numpy(s[mine].copy()).to(ctx.device)
         var.shard.import_rows(kt, wt, st_t)
-    ctx.barrier()

@@ -14,6 +14,8 @@ config strings keep working) but unused, and say so in their help. The
   server.report_interval  -> periodic metrics report (utils/metrics.Reporter)
   server.cache_size_mb    -> HBM row-cache budget of the host-DRAM tier
   server.update_early_return -> commit on a side stream (overlap analogue)
+  server.track_changes    -> new variables record which rows change, for
+                             delta checkpoints (checkpoint.dump_delta)
 """
 
 from __future__ import annotations
@@ -83,6 +85,8 @@ class ServerConfig:
     cache_size_mb: int = 0                # HBM row-cache budget (DRAM tier);
                                           # 0 = everything resident in HBM
     pmem_pool_root_path: str = ""         # host-DRAM tier spill dir analogue
+    track_changes: bool = False           # variables start with change
+                                          # tracking on (delta checkpoints)
 
     @classmethod
     def parse(cls, cfg: Dict[str, Any]) -> "ServerConfig":

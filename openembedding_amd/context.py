@@ -106,6 +106,10 @@ class Context:
         else:
             self.model_uuid = uuid.uuid4().hex
         self.model_version = 0
+        # base of the delta chain this context was loaded from
+        # (checkpoint.load_model / apply_delta)
+        self.loaded_epoch: Optional[int] = None
+        self.loaded_model_uuid: Optional[str] = None
         self._t0 = time.time()
         # typed config tree from flags.config (reference EnvConfig via
         # embed.flags.config YAML, openembedding/__init__.py:8-41)
@@ -169,6 +173,8 @@ class Context:
         shard = shard_cls(meta, shard_id=self.rank,
                           shard_num=self.world_size,
                           device=str(self.device), seed=self.seed, **kw)
+        if self.config.server.track_changes:
+            shard.track_changes(True)
         var = ShardedVariable(shard, storage)
         self.variables[vid] = var
         return var

@@ -363,3 +363,9 @@ class QuantizedShard:
 
     def set_optimizer(self, category, **cfg):
         self._read_only("set_optimizer")
+
+    def track_changes(self, enable: bool = True) -> None:
+        if enable:
+            raise NotImplementedError(
+                "QuantizedShard does not train, so it has no changes to "
+                "track: it receives deltas (import_rows), it cuts none")

@@ -278,3 +278,10 @@ class TieredVariableShard(VariableShard):
         self._touch = torch.zeros(0, dtype=torch.int64)
         self._cache_full_since_ckpt = False
         self._checkpoint_work_id = None
+
+    def track_changes(self, enable: bool = True) -> None:
+        if enable:
+            raise NotImplementedError(
+                "change tracking is per cache slot and the capacity tier "
+                "moves rows between slots on eviction: delta checkpoints "
+                "need an untiered variable (server.cache_size_mb = 0)")

@@ -352,3 +352,10 @@ class HipTieredVariableShard(HipVariableShard):
         self._cache_full_since_ckpt = False
         self._checkpoint_work_id = None
         self._evict_epoch += 1
+
+    def track_changes(self, enable: bool = True) -> None:
+        if enable:
+            raise NotImplementedError(
+                "change tracking is per cache slot and the capacity tier "
+                "moves rows between slots on eviction: delta checkpoints "
+                "need an untiered variable (server.cache_size_mb = 0)")

@@ -60,6 +60,9 @@ class VariableShard:
     """One rank's shard of one embedding variable (torch backend)."""
 
     GROW = 2
+    # change tracking for delta checkpoints (track_changes); while it is off
+    # no row_epoch tensor exists and no stamping runs
+    _tracking = False
 
     def __init__(self, meta: VariableMeta, shard_id: int = 0, shard_num: int = 1,
                  device: str = "cpu", seed: int = 0):
@@ -124,6 +127,8 @@ class VariableShard:
                         s = self.state[sl]
                         new_opt.train_init(s, self.dim)
                         self.state[sl] = s
+            if self._tracking:
+                self._stamp_live()  # the state block of every row changed
         self._state_init_row = self._make_state_init_row()
 
     def _make_state_init_row(self) -> torch.Tensor:
@@ -146,6 +151,8 @@ class VariableShard:
                         device=self.device)
         s[:cap] = self.state
         self.state = s
+        if self._tracking:
+            self._grow_row_epoch(new_cap)
 
     def _lookup_or_insert(self, keys: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """keys: unique int64 global keys owned by this shard.
@@ -194,6 +201,8 @@ class VariableShard:
             self.weights[ns] = self.initializer(self.seed, nk, self.dim, self.dtype)
             if self.state_dim:
                 self.state[ns] = self._state_init_row.expand(ns.numel(), -1)
+            if self._tracking:
+                self.row_epoch[ns] = self._epoch
         return slots, new_mask
 
     def _lookup_readonly(self, keys: torch.Tensor) -> torch.Tensor:
@@ -278,6 +287,8 @@ class VariableShard:
         self.optimizer.update(w, s, counts, grads)
         self.weights[slots] = w
         self.state[slots] = s
+        if self._tracking:
+            self.row_epoch[slots] = self._epoch
 
     # ------------------------------------------------------------- checkpoint
 
@@ -312,6 +323,8 @@ class VariableShard:
         self.weights[slots] = weights.to(self.device, self.dtype)
         if state is not None and self.state_dim:
             self.state[slots] = state.to(self.device, self.dtype)
+        if self._tracking:
+            self.row_epoch[slots] = self._epoch
 
     def get_weights(self, keys: torch.Tensor) -> torch.Tensor:
         return self.pull_readonly(keys)
@@ -325,7 +338,112 @@ class VariableShard:
                                        device=self.device)
             self.state = torch.zeros((0, self.state_dim), dtype=self.dtype,
                                      device=self.device)
+            if self._tracking:
+                self.row_epoch = self.row_epoch.new_zeros(0)
         else:
             self.valid.zero_()
             self.weights.zero_()
             self.state.zero_()
+            if self._tracking:
+                self.row_epoch.zero_()
+
+    # -------------------------------------------------------- change tracking
+    # Delta checkpoints (checkpoint.dump_delta): ``row_epoch[slot]`` is the
+    # epoch of the row's last write and ``epoch`` the current one. A row is
+    # stamped when a lookup-or-insert creates it, when update_weights applies
+    # the optimizer to it, when import_rows writes it and when set_optimizer
+    # rebuilds the state block; reads stamp nothing. Rows are never deleted,
+    # so the rows with ``row_epoch >= since`` are the whole difference. This
+    # torch form is the CPU path and the oracle of the HIP kernels.
+
+    def track_changes(self, enable: bool = True) -> None:
+        """Turn change tracking on (row_epoch zeroed, epoch 1) or off (the
+        tensors are dropped). Turning it on twice keeps the stamps."""
+        if not enable:
+            self._tracking = False
+            for name in ("row_epoch", "epoch_dev", "_epoch"):
+                if name in self.__dict__:
+                    delattr(self, name)
+            return
+        if self._tracking:
+            return
+        self.row_epoch = torch.zeros(self.weights.shape[0],
+                                     dtype=torch.int32, device=self.device)
+        self._epoch = 1
+        self._tracking = True
+
+    @property
+    def tracking(self) -> bool:
+        return self._tracking
+
+    @property
+    def epoch(self) -> int:
+        """The epoch that writes are stamped with (tracking only)."""
+        self._need_tracking()
+        return self._epoch
+
+    def set_epoch(self, epoch: int, reset: bool = False) -> None:
+        """Move to ``epoch``; ``reset`` also forgets every stamp (after a
+        base was loaded, so that the next delta does not re-emit it)."""
+        self._need_tracking()
+        if reset:
+            self.row_epoch.zero_()
+        self._epoch = int(epoch)
+
+    def _need_tracking(self) -> None:
+        if not self._tracking:
+            raise RuntimeError("change tracking is off: call "
+                               "track_changes() first")
+
+    def _grow_row_epoch(self, new_cap: int) -> None:
+        old = self.row_epoch
+        self.row_epoch = old.new_zeros(new_cap)
+        self.row_epoch[:old.numel()] = old
+
+    def _stamp_live(self) -> None:
+        if self.meta.use_hash_table:
+            self.row_epoch[:self._nrows] = self._epoch
+        else:
+            self.row_epoch[self.valid] = self._epoch
+
+    def _slot_key_list(self) -> torch.Tensor:
+        """slot -> key of the hash table's rows."""
+        sk = torch.empty(self._nrows, dtype=torch.int64)
+        if self._index:
+            ks = torch.tensor(list(self._index.keys()), dtype=torch.int64)
+            vs = torch.tensor(list(self._index.values()), dtype=torch.int64)
+            sk[vs] = ks
+        return sk.to(self.device)
+
+    def select_changed(self, since: int) -> Tuple[torch.Tensor, int]:
+        """(slots, n): the live rows with ``row_epoch >= since`` in
+        ascending slot order. ``slots`` may be longer than ``n``."""
+        self._need_tracking()
+        if self.meta.use_hash_table:
+            live = torch.zeros(self.row_epoch.numel(), dtype=torch.bool,
+                               device=self.device)
+            live[:self._nrows] = True
+        else:
+            live = self.valid
+        slots = (live & (self.row_epoch >= int(since))).nonzero(
+            as_tuple=True)[0]
+        return slots, int(slots.numel())
+
+    def export_changed(self, since: int, include_state: bool = True,
+                       selection=None):
+        """Yield the rows changed since epoch ``since`` as ``(keys, weights,
+        state or None)`` blocks of at most ``checkpoint.BLOCK_ROWS`` rows, in
+        ascending slot order. A block is valid until the next one is asked
+        for. ``selection`` is a ``select_changed(since)`` result to reuse."""
+        from .. import checkpoint
+        slots, n = selection if selection is not None \
+            else self.select_changed(since)
+        want_state = bool(include_state and self.state_dim)
+        sk = self._slot_key_list() if self.meta.use_hash_table else None
+        step = int(checkpoint.BLOCK_ROWS)
+        for start in range(0, n, step):
+            sl = slots[start:min(start + step, n)]
+            keys = sk[sl] if sk is not None \
+                else sl * self.shard_num + self.shard_id
+            yield (keys, self.weights[sl].clone(),
+                   self.state[sl].clone() if want_state else None)

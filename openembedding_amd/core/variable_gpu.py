@@ -122,6 +122,8 @@ class HipVariableShard(VariableShard):
         sk = torch.empty(new_cap, dtype=torch.int64, device=self.device)
         sk[:self.slot_keys.shape[0]] = self.slot_keys
         self.slot_keys = sk
+        if self._tracking:
+            self._grow_row_epoch(new_cap)
 
     def _maybe_rehash(self) -> None:
         if self._nrows_upper * 2 <= self._cap:
@@ -166,19 +168,31 @@ class HipVariableShard(VariableShard):
                     raise RuntimeError(
                         "hash-table insert path is not hipGraph-capturable "
                         "without reserve_rows()")
-                return self.ext.ht_lookup(self.tk, self.tv, keys,
-                                          self.nrows_dev, self.slot_keys,
-                                          True, u_dev)
-            self._ensure_rows(self._nrows_upper + n)
-            self._maybe_rehash()
+            else:
+                self._ensure_rows(self._nrows_upper + n)
+                self._maybe_rehash()
+                self._nrows_upper += n
             slots, new_mask = self.ext.ht_lookup(self.tk, self.tv, keys,
                                                  self.nrows_dev, self.slot_keys,
                                                  True, u_dev)
-            self._nrows_upper += n
         else:
             slots, new_mask = self.ext.array_touch(self.valid_u8, keys,
                                                    self.shard_num, u_dev)
+        if self._tracking:
+            self._mark(slots, new_mask, u_dev)  # created rows
         return slots, new_mask
+
+    def _mark(self, slots, mask=None, u_dev=None) -> None:
+        """Stamp the named rows with the current epoch (tracking only)."""
+        self.ext.mark_rows(slots, mask, u_dev, self.epoch_dev,
+                           self.row_epoch)
+
+    def _apply(self, opt_id, slots, grads, counts, cfg, u_dev) -> None:
+        """One optimizer application, then its rows' stamp when tracking."""
+        self.ext.apply_optimizer(opt_id, self.weights, self.state, slots,
+                                 grads.contiguous(), counts, cfg, u_dev)
+        if self._tracking:
+            self._mark(slots, None, u_dev)
 
     def _lookup_readonly(self, keys: torch.Tensor) -> torch.Tensor:
         if self.meta.use_hash_table:
@@ -312,8 +326,7 @@ class HipVariableShard(VariableShard):
             blocks = [self._merge_bounded(blocks)]
         # bounded blocks: slots known from pull, zero-sync apply
         for keys_buf, u_dev, slots, grads, counts in blocks:
-            self.ext.apply_optimizer(opt_id, self.weights, self.state, slots,
-                                     grads.contiguous(), counts, cfg, u_dev)
+            self._apply(opt_id, slots, grads, counts, cfg, u_dev)
         if self._pending:
             if len(self._pending) == 1:
                 keys, grads, counts = self._pending[0]
@@ -330,8 +343,7 @@ class HipVariableShard(VariableShard):
             slots, new_mask = self._lookup_or_insert(keys)
             # init rows that were pushed without a prior pull
             self._gather(keys, slots, new_mask, False)
-            self.ext.apply_optimizer(opt_id, self.weights, self.state, slots,
-                                     grads.contiguous(), counts, cfg, None)
+            self._apply(opt_id, slots, grads, counts, cfg, None)
         if self.meta.use_hash_table and not self._in_graph_capture():
             # every 16 commits: tighten the row-count bound (the D2H read
             # syncs the stream — a per-step sync costs a pipeline bubble;
@@ -403,6 +415,8 @@ class HipVariableShard(VariableShard):
         self.weights[slots] = weights.to(self.device, self.dtype)
         if state is not None and self.state_dim:
             self.state[slots] = state.to(self.device, self.dtype)
+        if self._tracking:
+            self._mark(slots)
         if self.meta.use_hash_table:
             self._nrows_exact = int(self.nrows_dev.item())
             self._nrows_upper = self._nrows_exact
@@ -420,6 +434,69 @@ class HipVariableShard(VariableShard):
             self.valid_u8.zero_()
             self.weights.zero_()
             self.state.zero_()
+        if self._tracking:
+            self.row_epoch.zero_()
+
+    # ------------------------------------------------------ change tracking
+    # The base class's contract on the device. The epoch lives in
+    # ``epoch_dev`` and the stamping kernel reads it through the pointer, so
+    # a captured step stamps the epoch that is current when it is replayed.
+
+    def track_changes(self, enable: bool = True) -> None:
+        was = self._tracking
+        super().track_changes(enable)
+        if enable and not was:
+            self.epoch_dev = torch.ones(1, dtype=torch.int32,
+                                        device=self.device)
+
+    def set_epoch(self, epoch: int, reset: bool = False) -> None:
+        super().set_epoch(epoch, reset)
+        self.epoch_dev.fill_(self._epoch)
+
+    def select_changed(self, since: int):
+        """(slots int64 [R] with a -1 tail, n_dev int32[1]), both on the
+        device: nothing is read on the host."""
+        self._need_tracking()
+        if self.meta.use_hash_table:
+            return self.ext.select_changed(self.row_epoch, int(since),
+                                           nrows_dev=self.nrows_dev)
+        return self.ext.select_changed(self.row_epoch, int(since),
+                                       valid=self.valid_u8)
+
+    def export_changed(self, since: int, include_state: bool = True,
+                       selection=None):
+        """The base class's contract without a copy of the slab: the extra
+        device memory is the slot list, its scratch and one staging block,
+        which every yielded block aliases (use a block before asking for
+        the next). The changed-row count is read on the host once, here."""
+        from .. import checkpoint
+        slots, n_dev = selection if selection is not None \
+            else self.select_changed(since)
+        n = n_dev if isinstance(n_dev, int) else int(n_dev.item())
+        if not n:
+            return
+        if isinstance(n_dev, int):
+            n_dev = torch.full((1,), n, dtype=torch.int32,
+                               device=self.device)
+        step = min(int(checkpoint.BLOCK_ROWS), n)
+        want_state = bool(include_state and self.state_dim)
+        k_out = torch.empty(step, dtype=torch.int64, device=self.device)
+        w_out = torch.empty((step, self.dim), dtype=self.dtype,
+                            device=self.device)
+        state = self.state if want_state else self.state[:, :0]
+        s_out = torch.empty((step, state.shape[1]), dtype=self.dtype,
+                            device=self.device)
+        hashed = self.meta.use_hash_table
+        for start in range(0, n, step):
+            cnt = min(step, n - start)
+            self.ext.gather_rows_by_slot(
+                self.weights, state,
+                slot_keys=self.slot_keys if hashed else None,
+                shard_num=self.shard_num, shard_id=self.shard_id,
+                slots=slots, start=start, count=cnt, n_dev=n_dev,
+                keys_out=k_out, w_out=w_out, s_out=s_out)
+            yield (k_out[:cnt], w_out[:cnt],
+                   s_out[:cnt] if want_state else None)
 
     # state handling shared with base -------------------------------------
 

@@ -103,6 +103,17 @@ void emb_bce_bwd(const float*, const float*, long, const float*, float*,
 void emb_bucketize_pad(const i64*, long, const int*, long, long, i64*, int*,
                        int*, int*, int*, hipStream_t_);
 void emb_mask_tail(i64*, float*, u64*, long, long, const int*, hipStream_t_);
+void emb_mark_rows(const i64*, long, const unsigned char*, const int*,
+                   const int*, int*, long, hipStream_t_);
+long emb_delta_tile_rows();
+long emb_delta_tiles(long);
+void emb_delta_count(const int*, long, int, const int*, const unsigned char*,
+                     int*, hipStream_t_);
+void emb_delta_compact(const int*, long, int, const int*,
+                       const unsigned char*, const int*, i64*, hipStream_t_);
+void emb_delta_gather(const float*, const float*, long, long, long,
+                      const i64*, long, long, const i64*, long, long, long,
+                      const int*, i64*, float*, float*, hipStream_t_);
 void emb_fault_in(const i64*, long, const int*, const u64*, const int*, long,
                   const float*, const float*, float*, float*, long, long,
                   const i64*, unsigned char*, int*, hipStream_t_);
@@ -906,6 +917,133 @@ void mask_tail(torch::Tensor keys, torch::Tensor grads, torch::Tensor counts,
                   u_ptr(u_dev), cur_stream());
 }
 
+// ---- delta checkpoints --------------------------------------------------
+
+void mark_rows(torch::Tensor slots, OptTensor mask, OptTensor u_dev,
+               torch::Tensor epoch_dev, torch::Tensor row_epoch) {
+    CHECK_GPU(slots); CHECK_CONT(slots);
+    CHECK_GPU(epoch_dev); CHECK_GPU(row_epoch); CHECK_CONT(row_epoch);
+    TORCH_CHECK(slots.dtype() == torch::kInt64, "slots must be int64");
+    TORCH_CHECK(epoch_dev.dtype() == torch::kInt32 && epoch_dev.numel() == 1,
+                "epoch_dev must be int32[1]");
+    TORCH_CHECK(row_epoch.dtype() == torch::kInt32,
+                "row_epoch must be int32");
+    const unsigned char* mp = nullptr;
+    if (mask.has_value()) {
+        CHECK_GPU(*mask); CHECK_CONT(*mask);
+        TORCH_CHECK(mask->element_size() == 1
+                    && mask->numel() == slots.numel(),
+                    "mask must hold one byte per slot");
+        mp = static_cast<const unsigned char*>(mask->data_ptr());
+    }
+    if (u_dev.has_value()) CHECK_GPU(*u_dev);
+    const c10::cuda::CUDAGuard guard(slots.device());
+    emb_mark_rows(slots.data_ptr<i64>(), slots.numel(), mp, u_ptr(u_dev),
+                  epoch_dev.data_ptr<int>(), row_epoch.data_ptr<int>(),
+                  row_epoch.numel(), cur_stream());
+}
+
+// rows with row_epoch >= since that are live, in ascending order:
+// (slots int64 [R], tail -1; n_dev int32 [1]). Count per tile, scan the
+// tile counts, compact; nothing is read on the host.
+std::tuple<torch::Tensor, torch::Tensor> select_changed(
+    torch::Tensor row_epoch, int64_t since, OptTensor nrows_dev,
+    OptTensor valid) {
+    CHECK_GPU(row_epoch); CHECK_CONT(row_epoch);
+    TORCH_CHECK(row_epoch.dtype() == torch::kInt32,
+                "row_epoch must be int32");
+    TORCH_CHECK(nrows_dev.has_value() != valid.has_value(),
+                "select_changed takes nrows_dev (hash) or valid (array)");
+    TORCH_CHECK(since >= INT32_MIN && since <= INT32_MAX, "since range");
+    long R = row_epoch.numel();
+    const int* np = nullptr;
+    const unsigned char* vp = nullptr;
+    if (nrows_dev.has_value()) {
+        CHECK_GPU(*nrows_dev);
+        TORCH_CHECK(nrows_dev->dtype() == torch::kInt32
+                    && nrows_dev->numel() == 1, "nrows_dev must be int32[1]");
+        np = nrows_dev->data_ptr<int>();
+    } else {
+        CHECK_GPU(*valid); CHECK_CONT(*valid);
+        TORCH_CHECK(valid->element_size() == 1 && valid->numel() == R,
+                    "valid must hold one byte per row");
+        vp = static_cast<const unsigned char*>(valid->data_ptr());
+    }
+    const c10::cuda::CUDAGuard guard(row_epoch.device());
+    auto i32 = row_epoch.options();
+    auto slots = torch::empty({R}, i32.dtype(torch::kInt64));
+    if (R == 0) return {slots, torch::zeros({1}, i32)};
+    long T = emb_delta_tiles(R);
+    auto counts = torch::empty({T}, i32);
+    emb_delta_count(row_epoch.data_ptr<int>(), R, (int)since, np, vp,
+                    counts.data_ptr<int>(), cur_stream());
+    auto incl = torch::cumsum(counts, 0, torch::kInt32);
+    emb_delta_compact(row_epoch.data_ptr<int>(), R, (int)since, np, vp,
+                      incl.data_ptr<int>(), slots.data_ptr<i64>(),
+                      cur_stream());
+    return {slots, incl.slice(0, T - 1, T)};
+}
+
+// rows of slots[start, start+count) -> (keys_out, w_out, s_out); positions
+// at or past *n_dev and slots outside the slab write nothing. The outputs
+// may be passed in, so that one staging block serves a whole export.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> gather_rows_by_slot(
+    torch::Tensor weights, torch::Tensor state, OptTensor slot_keys,
+    int64_t shard_num, int64_t shard_id, torch::Tensor slots, int64_t start,
+    int64_t count, torch::Tensor n_dev, OptTensor keys_out, OptTensor w_out,
+    OptTensor s_out) {
+    CHECK_GPU(weights); CHECK_CONT(weights); CHECK_CONT(state);
+    CHECK_GPU(slots); CHECK_CONT(slots); CHECK_GPU(n_dev);
+    TORCH_CHECK(weights.dim() == 2 && weights.dtype() == torch::kFloat32,
+                "weights must be float32 [R, dim]");
+    TORCH_CHECK(slots.dtype() == torch::kInt64, "slots must be int64");
+    TORCH_CHECK(n_dev.dtype() == torch::kInt32 && n_dev.numel() == 1,
+                "n_dev must be int32[1]");
+    TORCH_CHECK(start >= 0 && count >= 0, "start/count must be >= 0");
+    long R = weights.size(0), dim = weights.size(1);
+    long sd = (state.dim() == 2 && state.numel()) ? state.size(1) : 0;
+    if (sd) {
+        CHECK_GPU(state);
+        TORCH_CHECK(state.dtype() == torch::kFloat32 && state.size(0) >= R,
+                    "state must be float32 with a row per weights row");
+    }
+    const i64* sk = nullptr;
+    if (slot_keys.has_value()) {
+        CHECK_GPU(*slot_keys); CHECK_CONT(*slot_keys);
+        TORCH_CHECK(slot_keys->dtype() == torch::kInt64
+                    && slot_keys->numel() >= R,
+                    "slot_keys must be int64 with a key per weights row");
+        sk = slot_keys->data_ptr<i64>();
+    }
+    const c10::cuda::CUDAGuard guard(weights.device());
+    auto ko = keys_out.has_value() ? *keys_out
+        : torch::zeros({count}, slots.options());
+    auto wo = w_out.has_value() ? *w_out
+        : torch::zeros({count, dim}, weights.options());
+    auto so = s_out.has_value() ? *s_out
+        : torch::zeros({count, sd}, weights.options());
+    CHECK_GPU(ko); CHECK_CONT(ko); CHECK_GPU(wo); CHECK_CONT(wo);
+    CHECK_CONT(so);
+    TORCH_CHECK(ko.dtype() == torch::kInt64 && ko.numel() >= count,
+                "keys_out must be int64 [>= count]");
+    TORCH_CHECK(wo.dtype() == torch::kFloat32 && wo.dim() == 2
+                && wo.size(0) >= count && wo.size(1) == dim,
+                "w_out must be float32 [>= count, dim]");
+    if (sd) {
+        CHECK_GPU(so);
+        TORCH_CHECK(so.dtype() == torch::kFloat32 && so.dim() == 2
+                    && so.size(0) >= count && so.size(1) == sd,
+                    "s_out must be float32 [>= count, state_dim]");
+    }
+    emb_delta_gather(weights.data_ptr<float>(),
+                     sd ? state.data_ptr<float>() : nullptr, R, dim, sd, sk,
+                     shard_num, shard_id, slots.data_ptr<i64>(),
+                     slots.numel(), start, count, n_dev.data_ptr<int>(),
+                     ko.data_ptr<i64>(), wo.data_ptr<float>(),
+                     sd ? so.data_ptr<float>() : nullptr, cur_stream());
+    return {ko, wo, so};
+}
+
 // ---- capacity tier v2 --------------------------------------------------
 // Pinned host tensors are device-accessible on ROCm (hipHostMalloc-backed
 // via the torch pinned allocator): the fault-in/spill kernels read/write
@@ -1593,6 +1731,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("mask_tail", &mask_tail,
           "zero the garbage tail of a bounded block (enables multi-block "
           "merge by concatenation)");
+    m.def("mark_rows", &mark_rows,
+          "delta checkpoints: row_epoch[slot] = *epoch_dev for the named "
+          "rows (optional byte mask and device count)",
+          pybind11::arg("slots"), pybind11::arg("mask") = pybind11::none(),
+          pybind11::arg("u_dev") = pybind11::none(),
+          pybind11::arg("epoch_dev"), pybind11::arg("row_epoch"));
+    m.attr("DELTA_TILE_ROWS") = emb_delta_tile_rows();
+    m.def("select_changed", &select_changed,
+          "delta checkpoints: ascending slots of the live rows with "
+          "row_epoch >= since -> (slots [R] with a -1 tail, n_dev int32[1])",
+          pybind11::arg("row_epoch"), pybind11::arg("since"),
+          pybind11::arg("nrows_dev") = pybind11::none(),
+          pybind11::arg("valid") = pybind11::none());
+    m.def("gather_rows_by_slot", &gather_rows_by_slot,
+          "delta checkpoints: keys, weights and state of "
+          "slots[start:start+count] into staging buffers",
+          pybind11::arg("weights"), pybind11::arg("state"),
+          pybind11::arg("slot_keys") = pybind11::none(),
+          pybind11::arg("shard_num") = 1, pybind11::arg("shard_id") = 0,
+          pybind11::arg("slots"), pybind11::arg("start"),
+          pybind11::arg("count"), pybind11::arg("n_dev"),
+          pybind11::arg("keys_out") = pybind11::none(),
+          pybind11::arg("w_out") = pybind11::none(),
+          pybind11::arg("s_out") = pybind11::none());
     m.def("fault_in", &fault_in,
           "tier v2: copy host-resident rows into fresh cache slots, "
           "clearing their lazy-init mask");

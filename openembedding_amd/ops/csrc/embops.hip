@@ -2164,6 +2164,156 @@ __global__ void k_gather_host(const i64* __restrict__ keys, long n,
     for (long j = lane; j < dim; j += G) out[(u64)g * dim + j] = hw[j];
 }
 
+// ------------------------------------------------------ delta checkpoints
+// Change tracking for incremental dumps: row_epoch[slot] holds the epoch of
+// the row's last write; a delta is the rows with row_epoch >= since. The
+// current epoch is read THROUGH epoch_dev, so a captured step stamps the
+// epoch that is current at replay, not the one frozen at capture.
+
+// stamp: one thread per element; duplicates store the same value (benign)
+__global__ void k_mark_rows(const i64* __restrict__ slots, long n,
+                            const unsigned char* __restrict__ mask,
+                            const int* __restrict__ u_dev,
+                            const int* __restrict__ epoch_dev,
+                            int* __restrict__ row_epoch, long R) {
+    long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    if (u_dev && g >= *u_dev) return;
+    if (mask && !mask[g]) return;
+    i64 s = slots[g];
+    if (s < 0 || s >= R) return;
+    row_epoch[s] = *epoch_dev;
+}
+
+// Ordered stream compaction of the changed rows in three launches: per-tile
+// counts, a scan of the counts (the launcher's caller), and a compaction
+// that re-evaluates the predicate. No block ever waits for another. A tile
+// is DT_ITEMS rounds of one block; round i covers rows
+// [tile + i*BLOCK, tile + (i+1)*BLOCK), one row per thread (coalesced), so
+// ascending row order is (round, wave, lane).
+#define DT_ITEMS 8
+#define DT_TILE (BLOCK * DT_ITEMS)
+#define DT_WAVES (BLOCK / 64)
+
+DEV bool delta_pred(const int* __restrict__ row_epoch, int since, long r,
+                    long R, long live,
+                    const unsigned char* __restrict__ valid) {
+    if (r >= R) return false;
+    if (valid ? valid[r] == 0 : r >= live) return false;
+    return row_epoch[r] >= since;
+}
+
+DEV long delta_live(const int* __restrict__ nrows_dev, long R) {
+    if (!nrows_dev) return R;
+    long live = (long)*nrows_dev;
+    return live < 0 ? 0 : (live > R ? R : live);
+}
+
+__global__ __launch_bounds__(BLOCK)
+void k_delta_count(const int* __restrict__ row_epoch, long R, int since,
+                   const int* __restrict__ nrows_dev,
+                   const unsigned char* __restrict__ valid,
+                   int* __restrict__ tile_counts) {
+    __shared__ int wave_cnt[DT_WAVES];
+    long live = delta_live(nrows_dev, R);
+    long base = (long)blockIdx.x * DT_TILE + threadIdx.x;
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < DT_ITEMS; ++i) {
+        bool p = delta_pred(row_epoch, since, base + (long)i * BLOCK, R, live,
+                            valid);
+        c += __popcll(__ballot(p));
+    }
+    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+#pragma unroll
+        for (int w = 0; w < DT_WAVES; ++w) t += wave_cnt[w];
+        tile_counts[blockIdx.x] = t;
+    }
+}
+
+// tile_incl: inclusive scan of tile_counts over all T tiles
+__global__ __launch_bounds__(BLOCK)
+void k_delta_compact(const int* __restrict__ row_epoch, long R, int since,
+                     const int* __restrict__ nrows_dev,
+                     const unsigned char* __restrict__ valid,
+                     const int* __restrict__ tile_incl, long T,
+                     i64* __restrict__ slots) {
+    __shared__ int cnt[DT_ITEMS * DT_WAVES];
+    __shared__ int off[DT_ITEMS * DT_WAVES];
+    long live = delta_live(nrows_dev, R);
+    long base = (long)blockIdx.x * DT_TILE + threadIdx.x;
+    int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    bool p[DT_ITEMS];
+    int rank[DT_ITEMS];
+#pragma unroll
+    for (int i = 0; i < DT_ITEMS; ++i) {
+        p[i] = delta_pred(row_epoch, since, base + (long)i * BLOCK, R, live,
+                          valid);
+        u64 b = __ballot(p[i]);
+        rank[i] = __popcll(b & below);
+        if (lane == 0) cnt[i * DT_WAVES + wave] = __popcll(b);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int j = 0; j < DT_ITEMS * DT_WAVES; ++j) {
+            off[j] = run;
+            run += cnt[j];
+        }
+    }
+    __syncthreads();
+    long total = (long)tile_incl[T - 1];
+    long tile_base = blockIdx.x ? (long)tile_incl[blockIdx.x - 1] : 0;
+#pragma unroll
+    for (int i = 0; i < DT_ITEMS; ++i) {
+        long r = base + (long)i * BLOCK;
+        if (p[i]) {
+            long pos = tile_base + off[i * DT_WAVES + wave] + rank[i];
+            if (pos >= 0 && pos < R) slots[pos] = r;
+        }
+        // the tail of the list: position r is past every compacted entry
+        if (r < R && r >= total) slots[r] = -1;
+    }
+}
+
+// gather the rows of slots[start, start+count) into staging buffers; one
+// G-lane group per row, keys from slot_keys (hash) or the array layout
+template <int G>
+__global__ void k_delta_gather(const float* __restrict__ weights,
+                               const float* __restrict__ state, long R,
+                               long dim, long sd,
+                               const i64* __restrict__ slot_keys,
+                               long shard_num, long shard_id,
+                               const i64* __restrict__ slots, long nslots,
+                               long start, long count,
+                               const int* __restrict__ n_dev,
+                               i64* __restrict__ keys_out,
+                               float* __restrict__ w_out,
+                               float* __restrict__ s_out) {
+    long g = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    int lane = threadIdx.x % G;
+    if (g >= count) return;
+    long pos = start + g;
+    if (pos < 0 || pos >= nslots || pos >= (long)*n_dev) return;
+    i64 slot = slots[pos];
+    if (slot < 0 || slot >= R) return;
+    if (lane == 0)
+        keys_out[g] = slot_keys ? slot_keys[slot]
+                                : slot * shard_num + shard_id;
+    const float* wrow = weights + (u64)slot * dim;
+    float* wo = w_out + (u64)g * dim;
+    for (long j = lane; j < dim; j += G) wo[j] = wrow[j];
+    if (sd > 0) {
+        const float* srow = state + (u64)slot * sd;
+        float* so = s_out + (u64)g * sd;
+        for (long j = lane; j < sd; j += G) so[j] = srow[j];
+    }
+}
+
 // ============================================================== launchers
 
 // shared dispatch ladder of the plain and the bag-indirected reduce
@@ -2705,6 +2855,52 @@ void emb_mask_tail(i64* keys, float* grads, u64* counts, long n, long dim,
         k_mask_tail<<<grid1d(n * dim), BLOCK, 0, stream>>>(keys, grads,
                                                            counts, n, dim,
                                                            u_dev);
+}
+
+void emb_mark_rows(const i64* slots, long n, const unsigned char* mask,
+                   const int* u_dev, const int* epoch_dev, int* row_epoch,
+                   long R, hipStream_t stream) {
+    if (n && R)
+        k_mark_rows<<<grid1d(n), BLOCK, 0, stream>>>(slots, n, mask, u_dev,
+                                                     epoch_dev, row_epoch, R);
+}
+
+long emb_delta_tile_rows() { return DT_TILE; }
+long emb_delta_tiles(long R) { return (R + DT_TILE - 1) / DT_TILE; }
+
+void emb_delta_count(const int* row_epoch, long R, int since,
+                     const int* nrows_dev, const unsigned char* valid,
+                     int* tile_counts, hipStream_t stream) {
+    if (R)
+        k_delta_count<<<(int)emb_delta_tiles(R), BLOCK, 0, stream>>>(
+            row_epoch, R, since, nrows_dev, valid, tile_counts);
+}
+
+void emb_delta_compact(const int* row_epoch, long R, int since,
+                       const int* nrows_dev, const unsigned char* valid,
+                       const int* tile_incl, i64* slots,
+                       hipStream_t stream) {
+    long T = emb_delta_tiles(R);
+    if (R)
+        k_delta_compact<<<(int)T, BLOCK, 0, stream>>>(
+            row_epoch, R, since, nrows_dev, valid, tile_incl, T, slots);
+}
+
+void emb_delta_gather(const float* weights, const float* state, long R,
+                      long dim, long sd, const i64* slot_keys,
+                      long shard_num, long shard_id, const i64* slots,
+                      long nslots, long start, long count, const int* n_dev,
+                      i64* keys_out, float* w_out, float* s_out,
+                      hipStream_t stream) {
+    if (count <= 0 || !R) return;
+    if (dim <= 32)
+        k_delta_gather<16><<<grid1d(count * 16), BLOCK, 0, stream>>>(
+            weights, state, R, dim, sd, slot_keys, shard_num, shard_id,
+            slots, nslots, start, count, n_dev, keys_out, w_out, s_out);
+    else
+        k_delta_gather<64><<<grid1d(count * 64), BLOCK, 0, stream>>>(
+            weights, state, R, dim, sd, slot_keys, shard_num, shard_id,
+            slots, nslots, start, count, n_dev, keys_out, w_out, s_out);
 }
 
 void emb_fault_in(const i64* keys, long n, const int* u_dev, const u64* htk,

@@ -178,6 +178,10 @@ class ServedModel:
         self.created_at = time.time()
         self.variables: Dict[int, ServedVariable] = {}
         self.meta: Optional[dict] = None
+        # base of the delta chain (a dump written with change tracking on)
+        self.loaded_epoch: Optional[int] = None
+        self.model_uuid: Optional[str] = None
+        self._update_lock = threading.Lock()
 
     def load(self, device: str = "cpu",
              quantize: Optional[str] = None) -> None:
@@ -194,28 +198,94 @@ class ServedModel:
         reserved from the row counts in the dump's section headers."""
         quantize = check_quantize(quantize)
         meta = read_meta(self.uri)
+        if "delta" in meta:
+            raise RuntimeError(f"{self.uri} is a delta checkpoint: load its "
+                               "base, then apply_delta")
         self.meta = meta
         self.quantize = quantize
         shards: Dict[int, VariableShard] = {}
         for mvar in meta["variables"]:
             shards[mvar["variable_id"]] = _make_shard(mvar, device, quantize)
+        self._import(self.uri, meta, shards)
+        self.variables = {vid: ServedVariable(sh)
+                          for vid, sh in shards.items()}
+        self.loaded_epoch = meta.get("epoch")
+        self.model_uuid = meta.get("model_uuid")
+        self.status = ModelStatus.NORMAL
+
+    def _import(self, uri: str, meta: dict, shards: dict,
+                update: bool = False) -> int:
+        """Stream the rows of a dump or a delta into ``shards``. A load
+        reserves a quantized table exactly, section by section; an
+        ``update`` of a live one makes room only when the section could
+        outgrow the slab (its keys may all exist already), and then by at
+        least half the slab, so that a chain of deltas copies the slab a
+        logarithmic number of times."""
+        quantize = getattr(self, "quantize", None)
         section = None
-        for hdr, keys, w, _s in iter_blocks(self.uri, meta):
+        rows = 0
+        for hdr, keys, w, _s in iter_blocks(uri, meta):
             sh = shards.get(hdr["variable_id"])
             if sh is None or not len(keys):
                 continue
             if quantize is not None and hdr is not section:
                 section = hdr       # one header per (file, variable) section
-                if "num_items" in hdr:
-                    sh.reserve_rows(sh.num_rows + int(hdr["num_items"]))
+                if "num_items" in hdr and sh.meta.use_hash_table:
+                    need = sh.num_rows + int(hdr["num_items"])
+                    cap = sh.slab.shape[0]
+                    if not update:
+                        sh.reserve_rows(need)
+                    elif need > cap:
+                        sh.reserve_rows(max(need, cap + cap // 2))
             # frombuffer arrays are read-only; copy before wrapping (torch
             # tensors over read-only memory are undefined behavior)
             kt = torch.from_numpy(keys.copy())
             wt = torch.from_numpy(w.copy())
             sh.import_rows(kt.to(sh.device), wt.to(sh.device))
-        self.variables = {vid: ServedVariable(sh)
-                          for vid, sh in shards.items()}
-        self.status = ModelStatus.NORMAL
+            rows += len(keys)
+        return rows
+
+    def apply_delta(self, uri: str) -> dict:
+        """Upsert a delta checkpoint into the live tables, whatever their
+        row format: each row goes through the shard's ``import_rows``, which
+        overwrites an existing key and, on a quantized table, quantizes the
+        row into place. Refused with RuntimeError, before anything changes,
+        unless the delta continues this model's chain
+        (``checkpoint.check_delta``).
+
+        A block that a quantized table cannot hold (``ValueError`` from its
+        ``import_rows``: a non-finite value, an fp16 overflow) stops the
+        update there: the blocks before it stay applied and the epoch stays
+        where it was, so that the corrected delta can be applied again.
+
+        Readers are not locked out, and nothing orders a read against an
+        update: rows are written block by block, each row by one copy or
+        one quantizing kernel, and a read that overlaps the update may see
+        rows and variables of both epochs, may miss a key that the update
+        is creating (a table that grows swaps its buffers), and on a CPU
+        table may even catch a row mid-copy. A caller that needs a
+        consistent view quiesces reads around the call or updates a second
+        replica and switches. Updates of one model are serialized."""
+        from .checkpoint import check_delta
+        with self._update_lock:
+            if self.status != ModelStatus.NORMAL:
+                raise RuntimeError(
+                    f"model {self.sign!r} status {self.status}")
+            meta = read_meta(uri)
+            d = check_delta(meta, self.model_uuid, self.loaded_epoch)
+            shards = {vid: v.shard for vid, v in self.variables.items()}
+            for mvar in meta["variables"]:
+                sh = shards.get(mvar["variable_id"])
+                if sh is None or sh.dim != mvar["embedding_dim"]:
+                    raise RuntimeError(
+                        f"delta variable {mvar['variable_id']} does not "
+                        "match the loaded model")
+            try:
+                rows = self._import(uri, meta, shards, update=True)
+            finally:
+                self._export_cache = {}  # replica pages must show the update
+            self.loaded_epoch = d["epoch"]
+        return {"since": d["since"], "epoch": d["epoch"], "rows": rows}
 
     def export_block(self, variable_id: int, start: int, count: int):
         """Row block [start, start+count) of a variable in export order —
@@ -288,6 +358,9 @@ class ServedModel:
             "uri": self.uri,
             "status": self.status,
             "error": self.error,
+            # epoch of the dump plus the deltas applied since (None for a
+            # dump written without change tracking)
+            "epoch": self.loaded_epoch,
             "variables": ([
                 {"variable_id": v["variable_id"],
                  "embedding_dim": v["embedding_dim"],
@@ -418,6 +491,17 @@ class ModelController:
             threading.Thread(target=_load, daemon=True).start()
         return model
 
+    def update_model(self, sign: str, delta_uri: str) -> ServedModel:
+        """Apply a delta checkpoint to the live model ``sign`` in place
+        (``ServedModel.apply_delta``); the model keeps answering meanwhile.
+        KeyError for an unknown sign, RuntimeError for a delta that does
+        not continue the model's chain."""
+        m = self.manager.get(sign)
+        if m is None:
+            raise KeyError(f"model {sign!r} not found")
+        m.apply_delta(delta_uri)
+        return m
+
     def delete_model(self, sign: str) -> None:
         m = self.manager._remove(sign)
         if m is None:
@@ -535,6 +619,8 @@ def make_app(controller: Optional[ModelController] = None,
       GET    /models            list
       GET    /models/{sign}     describe
       DELETE /models/{sign}
+      POST   /models/{sign}/deltas   {"model_uri": <delta checkpoint>}
+                                apply a delta to the live model in place
       GET    /nodes             list nodes
       DELETE /nodes/{id}        request shutdown
       POST   /models/{sign}/variables/{vid}/pull   {"indices": [[...]]}
@@ -562,6 +648,9 @@ def make_app(controller: Optional[ModelController] = None,
         from_replica: Optional[str] = None
         # serve from packed tables: "int8" | "fp16" (anything else: 422)
         quantize: Optional[str] = None
+
+    class UpdateModelReq(BaseModel):
+        model_uri: str
 
     class PullReq(BaseModel):
         indices: list
@@ -597,6 +686,25 @@ def make_app(controller: Optional[ModelController] = None,
             raise HTTPException(status_code=409, detail=str(e))
         except (FileNotFoundError, RuntimeError) as e:
             raise HTTPException(status_code=400, detail=str(e))
+        return m.describe()
+
+    @app.post("/models/{sign}/deltas")
+    def update_model(sign: str, req: UpdateModelReq):
+        """Apply a delta checkpoint to a live model; answers with the
+        model's description at the new epoch. 404 unknown sign, 409 a delta
+        that does not continue the chain, 400 an unreadable URI, 422 rows
+        that the table's format cannot hold (the blocks before them stay
+        applied, the epoch does not move)."""
+        try:
+            m = controller.update_model(sign, req.model_uri)
+        except KeyError as e:
+            raise HTTPException(status_code=404, detail=str(e))
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        except FileNotFoundError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        except RuntimeError as e:
+            raise HTTPException(status_code=409, detail=str(e))
         return m.describe()
 
     @app.get("/models/{sign}/variables/{variable_id}/rows")

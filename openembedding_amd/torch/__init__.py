@@ -36,7 +36,8 @@ __all__ = [
     "Embedding", "EmbeddingBag", "CombinedEmbedding", "Variable", "Context",
     "distributed_optimizer", "DistributedOptimizer", "distributed_model",
     "Model", "save_server_model", "load_server_model",
-    "save_as_original_model", "pulling", "sparse_read_as_dense",
+    "track_server_model_changes", "save_server_model_delta",
+    "load_server_model_delta", "save_as_original_model", "pulling", "sparse_read_as_dense",
     "should_persist_server_model", "persist_server_model",
     "restore_server_model", "get_context",
     "Adadelta", "Adagrad", "Adam", "Adamax", "Ftrl", "Nadam", "NAdam",
@@ -952,6 +953,37 @@ def save_server_model(path: str, include_optimizer: bool = True):
 def load_server_model(path: str):
     from ..checkpoint import load_model
     load_model(get_context(), path)
+
+
+def track_server_model_changes(enable: bool = True):
+    """Record which rows change, on every existing variable and on those
+    created later — the precondition of ``save_server_model_delta``. Call it
+    before training (rows changed earlier are not in any delta; the next
+    full save is the base). Off by default: tracking adds two small kernel
+    launches per variable and step. Tiered variables cannot be tracked."""
+    ctx = get_context()
+    for v in ctx.variables.values():
+        v.shard.track_changes(enable)
+    ctx.config.server.track_changes = bool(enable)
+
+
+def save_server_model_delta(path: str, include_optimizer: bool = True,
+                            since: Optional[int] = None) -> dict:
+    """Write only the rows changed since the last save of either kind (or
+    since epoch ``since``); returns ``{"since", "epoch", "rows"}``. A
+    serving model takes it with ``ServedModel.apply_delta`` /
+    ``POST /models/{sign}/deltas``, a trainer with
+    ``load_server_model_delta``."""
+    from ..checkpoint import dump_delta
+    return dump_delta(get_context(), path,
+                      include_optimizer=include_optimizer, since=since)
+
+
+def load_server_model_delta(path: str) -> dict:
+    """Apply a delta on top of the loaded model, in place
+    (``checkpoint.apply_delta``)."""
+    from ..checkpoint import apply_delta
+    return apply_delta(get_context(), path)
 
 
 def save_as_original_model(model: nn.Module, path: str,
