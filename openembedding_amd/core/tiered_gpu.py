@@ -156,6 +156,12 @@ class HipTieredVariableShard(HipVariableShard):
         self._last_batch_upper = max(self._last_batch_upper, keys.numel())
         return slots, new_mask
 
+    # pushes reduce at push time and go through push_slots' stale-handle
+    # check below
+    fused_apply = False
+    # and pulls fault rows in between the lookup and the gather
+    fused_pull = False
+
     def push_slots(self, keys_buf, u_dev, slots, grads, counts) -> None:
         if getattr(slots, "_oe_epoch", self._evict_epoch) != self._evict_epoch:
             raise RuntimeError(

@@ -75,6 +75,12 @@ class HipVariableShard(VariableShard):
     # every row lives in the HBM slab, so pull_pooled_readonly is one fused
     # launch (the capacity tier turns this off)
     fused_pooled_readonly = True
+    # update_weights can sum an unreduced indexed block and apply it in one
+    # launch (push_index); the capacity tier turns this off
+    fused_apply = True
+    # pull_bounded_fused serves the flat bounded pull (dedup stopped after
+    # assign + one merged kernel); the capacity tier turns this off
+    fused_pull = True
 
     def __init__(self, meta: VariableMeta, shard_id: int = 0, shard_num: int = 1,
                  device: str = "cuda", seed: int = 0):
@@ -234,6 +240,39 @@ class HipVariableShard(VariableShard):
                            inverse=inverse, u_dev=u_dev)
         return out, slots
 
+    def pull_bounded_fused(self, flat: torch.Tensor, field_offsets=None,
+                           want_out: bool = True):
+        """``unique_bounded_indexed`` + ``pull_bounded`` with two launches
+        fewer: the dedup stops after its assign kernel (which touches an
+        array table on the way) and one merged kernel resolves the inverse,
+        files the index and gathers / lazily initialises. A hash table keeps
+        its lookup launch between the two. ``flat`` is the dedup's input
+        (raw field ids with ``field_offsets``). Returns (out [n, dim], uk,
+        inverse, u_dev, index, slots) as the two calls give them; ``out`` is
+        empty without ``want_out`` (rows are still initialised)."""
+        hash_mode = self.meta.use_hash_table
+        r = self.ext.unique_bounded_assign(
+            flat, field_offsets, None if hash_mode else self.valid_u8,
+            self.shard_num)
+        uk, inverse, u_dev = r[0], r[1], r[2]
+        index = tuple(r[3:8])
+        slot_of, tv, toff, rank, slots, new_mask = r[8:14]
+        if hash_mode:
+            slots, new_mask = self._lookup_or_insert(uk, u_dev)
+        cat, p0, p1, p2 = _init_params(self.initializer)
+        sir = self._state_init_row
+        if sir is None:
+            sir = self._make_state_init_row()
+            self._state_init_row = sir
+        out = self.ext.pull_merged(
+            self.weights, self.state, flat, field_offsets, slot_of, tv, toff,
+            rank, inverse, index[2], slots, new_mask,
+            0 if hash_mode else self.valid_u8.numel(), self.shard_num, cat,
+            p0, p1, p2, self.seed, sir.reshape(-1), want_out, u_dev)
+        if self._tracking and not hash_mode:
+            self._mark(slots, new_mask, u_dev)  # created rows
+        return out, uk, inverse, u_dev, index, slots
+
     def pull_pooled_bounded(self, keys_buf: torch.Tensor,
                             u_dev: torch.Tensor, inverse: torch.Tensor,
                             offsets: torch.Tensor, mode: int,
@@ -274,6 +313,24 @@ class HipVariableShard(VariableShard):
         """Queue a bounded pre-reduced block whose table slots are already
         known (saved from the matching pull)."""
         self._pending_bounded.append((keys_buf, u_dev, slots, grads, counts))
+
+    def push_index(self, keys_buf, u_dev, slots, grads, index) -> None:
+        """Queue a bounded block UNREDUCED: ``grads`` is the per-element
+        gradient [n, dim] (contiguous float32, held by reference until the
+        commit) and ``index`` the batch's inverted index. ``update_weights``
+        sums and applies it in one launch when it is the variable's only
+        pending block, and reduces it first otherwise."""
+        self._pending_bounded.append((keys_buf, u_dev, slots, grads, None,
+                                      tuple(index)))
+
+    def _reduce_block(self, block):
+        """A queued block in its reduced form (keys_buf, u_dev, slots,
+        ugrads, counts)."""
+        if len(block) == 5:
+            return block
+        keys_buf, u_dev, slots, grads, _, index = block
+        ugrads, counts = self.ext.reduce_by_index(*index, grads, u_dev)
+        return keys_buf, u_dev, slots, ugrads, counts
 
     def pull_readonly(self, keys: torch.Tensor) -> torch.Tensor:
         slots = self._lookup_readonly(keys)
@@ -317,6 +374,17 @@ class HipVariableShard(VariableShard):
         cfg = _opt_cfg_vector(self.optimizer)
         blocks = self._pending_bounded
         self._pending_bounded = []
+        if len(blocks) == 1 and len(blocks[0]) == 6 and not self._pending:
+            # the variable's only block, still unreduced: the segmented
+            # reduce applies every summed row where it forms it
+            keys_buf, u_dev, slots, grads, _, index = blocks[0]
+            self.ext.reduce_apply_by_index(opt_id, self.weights, self.state,
+                                           slots, *index, grads, cfg, u_dev)
+            if self._tracking:
+                self._mark(slots, None, u_dev)
+            blocks = []
+        else:
+            blocks = [self._reduce_block(b) for b in blocks]
         if len(blocks) > 1:
             # several pulls committed together: reference semantics
             # (MpscGradientReducer.h:30-53) are ONE optimizer step per

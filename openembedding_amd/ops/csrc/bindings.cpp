@@ -30,11 +30,25 @@ void emb_unique_indexed(const i64*, long, u64*, int*, long, int*,
                         unsigned char*, i64*, i64*, int*, const i64*, int,
                         int*, int*, int*, int*, int*, int*, int*, long, int*,
                         int*, hipStream_t_);
+void emb_unique_indexed_assign(const i64*, long, u64*, int*, long, int*,
+                               unsigned char*, i64*, i64*, int*, const i64*,
+                               int, int*, int*, int*, int*, int*, int*, int*,
+                               long, int*, int*, unsigned char*, long, long,
+                               i64*, unsigned char*, hipStream_t_);
+void emb_pull_merged(float*, float*, long, long, const i64*, const i64*, int,
+                     long, const int*, const int*, const int*, const int*,
+                     i64*, int*, i64*, unsigned char*, int, long, long,
+                     float*, int, float, float, float, u64, const float*,
+                     const int*, hipStream_t_);
 int emb_seg_threshold();
 int emb_seg_max_dim();
 void emb_reduce_by_index(const int*, const int*, const int*, const int*,
                          const int*, long, const float*, long, long,
                          const int*, float*, u64*, hipStream_t_);
+void emb_reduce_apply_by_index(int, const int*, const int*, const int*,
+                               const int*, const int*, long, const float*,
+                               long, long, const int*, const i64*, float*,
+                               float*, long, const float*, hipStream_t_);
 void emb_ht_lookup(u64*, int*, long, const i64*, long, int*, i64*, i64*,
                    unsigned char*, int, const int*, long, hipStream_t_);
 void emb_ht_rehash(const u64*, const int*, long, u64*, int*, long,
@@ -184,7 +198,9 @@ const int* u_ptr(const OptTensor& u_dev) {
 // counter} and, when ``indexed``, {seg_off, seg_cnt, perm, long_list,
 // n_long} behind them
 std::vector<torch::Tensor> unique_bounded_impl(
-    torch::Tensor keys, OptTensor field_offsets, bool indexed) {
+    torch::Tensor keys, OptTensor field_offsets, bool indexed,
+    bool stop_after_assign = false, OptTensor valid = c10::nullopt,
+    int64_t shard_num = 1) {
     CHECK_GPU(keys); CHECK_CONT(keys);
     TORCH_CHECK(keys.dtype() == torch::kInt64);
     const i64* foff = nullptr;
@@ -230,6 +246,36 @@ std::vector<torch::Tensor> unique_bounded_impl(
     auto seg_off = segs.select(0, 0), seg_cnt = segs.select(0, 1);
     auto perm = segs.select(0, 2), rank = segs.select(0, 3);
     auto n_long = ctr.narrow(0, 16, 1);
+    if (stop_after_assign) {
+        // the form k_pull_merged continues from: the scratch it resolves
+        // (slot_of, tv, toff, rank) comes back beside the results, and the
+        // array touch runs inside the assign kernel when ``valid`` is given
+        auto slots = torch::empty({n}, opts_i64);
+        auto new_mask = torch::empty({n}, opts_u8);
+        unsigned char* vptr = nullptr;
+        long vcap = 0;
+        if (valid.has_value()) {
+            CHECK_GPU(*valid); CHECK_CONT(*valid);
+            TORCH_CHECK(valid->dtype() == torch::kUInt8 && shard_num >= 1,
+                        "unique_bounded_assign: valid must be uint8");
+            vptr = valid->data_ptr<uint8_t>();
+            vcap = valid->numel();
+        }
+        emb_unique_indexed_assign(
+            keys.data_ptr<i64>(), n, (u64*)tk.data_ptr<i64>(),
+            tv.data_ptr<int>(), cap, slot_of.data_ptr<int>(),
+            is_first.data_ptr<uint8_t>(), uk.data_ptr<i64>(),
+            inverse.data_ptr<i64>(), counter.data_ptr<int>(), foff, F,
+            tct.data_ptr<int>(), tct.data_ptr<int>() + cap,
+            rank.data_ptr<int>(), seg_off.data_ptr<int>(),
+            seg_cnt.data_ptr<int>(), perm.data_ptr<int>(),
+            long_list.data_ptr<int>(), long_cap, ctr.data_ptr<int>(),
+            n_long.data_ptr<int>(), vptr, shard_num, vcap,
+            slots.data_ptr<i64>(), new_mask.data_ptr<uint8_t>(),
+            cur_stream());
+        return {uk, inverse, counter, seg_off, seg_cnt, perm, long_list,
+                n_long, slot_of, tv, tct.select(0, 1), rank, slots, new_mask};
+    }
     emb_unique_indexed(keys.data_ptr<i64>(), n, (u64*)tk.data_ptr<i64>(),
                        tv.data_ptr<int>(), cap, slot_of.data_ptr<int>(),
                        is_first.data_ptr<uint8_t>(), uk.data_ptr<i64>(),
@@ -258,6 +304,102 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
 unique_bounded_indexed(torch::Tensor keys, OptTensor field_offsets) {
     auto r = unique_bounded_impl(keys, field_offsets, true);
     return {r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]};
+}
+
+// unique_bounded_indexed without its last kernel, for pull_merged: returns
+// {uk, inverse, u_dev, seg_off, seg_cnt, perm, long_list, n_long, slot_of,
+// tv, toff, rank, slots, new_mask}. inverse and perm are completed by
+// pull_merged. With ``valid`` (array table) the assign kernel also touches
+// the table: slots / new_mask are filled below u_dev and valid is updated;
+// without it they come back unset, for ht_lookup's results.
+std::vector<torch::Tensor> unique_bounded_assign(
+    torch::Tensor keys, OptTensor field_offsets, OptTensor valid,
+    int64_t shard_num) {
+    return unique_bounded_impl(keys, field_offsets, true, true, valid,
+                               shard_num);
+}
+
+// The rest of a bounded pull after unique_bounded_assign (and ht_lookup for
+// a hash table): inverse, perm and gather + lazy init in one launch.
+// ``array_cap`` > 0: array table of that many rows, the slot comes from the
+// element's own key and the tail of slots / new_mask is written here;
+// 0: slots [n] is read per uid. ``keys`` is the dedup's input (raw field ids
+// with ``field_offsets``).
+torch::Tensor pull_merged(torch::Tensor weights, torch::Tensor state,
+                          torch::Tensor keys, OptTensor field_offsets,
+                          torch::Tensor slot_of, torch::Tensor tv,
+                          torch::Tensor toff, torch::Tensor rank,
+                          torch::Tensor inverse, torch::Tensor perm,
+                          torch::Tensor slots, torch::Tensor new_mask,
+                          int64_t array_cap, int64_t shard_num,
+                          int64_t init_cat, double p0, double p1, double p2,
+                          int64_t seed, torch::Tensor state_init_row,
+                          bool want_out, torch::Tensor u_dev) {
+    CHECK_GPU(weights); CHECK_CONT(weights);
+    CHECK_GPU(keys); CHECK_CONT(keys);
+    TORCH_CHECK(weights.dtype() == torch::kFloat32 && weights.dim() == 2
+                && keys.dtype() == torch::kInt64, "pull_merged dtypes");
+    long n = keys.numel();
+    TORCH_CHECK(n < (1L << 31), "pull_merged: n must fit int32");
+    for (const auto* t : {&slot_of, &tv, &toff, &rank, &perm, &u_dev}) {
+        CHECK_GPU(*t); CHECK_CONT(*t);
+        TORCH_CHECK(t->dtype() == torch::kInt32,
+                    "pull_merged: index tensors must be int32");
+    }
+    CHECK_GPU(inverse); CHECK_CONT(inverse); CHECK_GPU(slots);
+    CHECK_CONT(slots); CHECK_GPU(new_mask); CHECK_CONT(new_mask);
+    TORCH_CHECK(inverse.dtype() == torch::kInt64
+                && slots.dtype() == torch::kInt64
+                && new_mask.dtype() == torch::kUInt8, "pull_merged dtypes");
+    TORCH_CHECK(slot_of.numel() == n && rank.numel() == n
+                && perm.numel() == n && inverse.numel() == n
+                && slots.numel() == n && new_mask.numel() == n
+                && tv.numel() == toff.numel() && u_dev.numel() == 1,
+                "pull_merged: scratch does not match keys");
+    TORCH_CHECK(array_cap >= 0 && array_cap <= weights.size(0)
+                && shard_num >= 1, "pull_merged: array_cap beyond the table");
+    const i64* foff = nullptr;
+    int F = 0;
+    if (field_offsets.has_value() && field_offsets->numel()) {
+        CHECK_GPU(*field_offsets); CHECK_CONT(*field_offsets);
+        TORCH_CHECK(field_offsets->dtype() == torch::kInt64
+                    && n % field_offsets->numel() == 0,
+                    "pull_merged: field_offsets");
+        foff = field_offsets->data_ptr<i64>();
+        F = (int)field_offsets->numel();
+    }
+    const c10::cuda::CUDAGuard guard(weights.device());
+    long dim = weights.size(1);
+    long sd = state.numel() ? state.size(1) : 0;
+    if (sd) {
+        CHECK_GPU(state); CHECK_CONT(state);
+        CHECK_GPU(state_init_row); CHECK_CONT(state_init_row);
+        TORCH_CHECK(state.size(0) == weights.size(0)
+                    && state_init_row.numel() >= sd,
+                    "pull_merged: state does not match the table");
+    }
+    torch::Tensor out;
+    float* out_ptr = nullptr;
+    if (want_out) {
+        out = torch::empty({n, dim}, weights.options());
+        out_ptr = out.data_ptr<float>();
+    } else {
+        out = torch::empty({0}, weights.options());
+    }
+    if (init_cat == 1) p1 = p1 - p0;   // the span, as gather_init passes it
+    emb_pull_merged(weights.data_ptr<float>(),
+                    sd ? state.data_ptr<float>() : nullptr, dim, sd,
+                    keys.data_ptr<i64>(), foff, F, n,
+                    slot_of.data_ptr<int>(), tv.data_ptr<int>(),
+                    toff.data_ptr<int>(), rank.data_ptr<int>(),
+                    inverse.data_ptr<i64>(), perm.data_ptr<int>(),
+                    slots.data_ptr<i64>(), new_mask.data_ptr<uint8_t>(),
+                    array_cap > 0 ? 1 : 0, shard_num, array_cap, out_ptr,
+                    (int)init_cat, (float)p0, (float)p1, (float)p2,
+                    (u64)seed,
+                    sd ? state_init_row.data_ptr<float>() : nullptr,
+                    u_dev.data_ptr<int>(), cur_stream());
+    return out;
 }
 
 std::tuple<torch::Tensor, torch::Tensor> unique_inverse(torch::Tensor keys) {
@@ -402,6 +544,60 @@ std::tuple<torch::Tensor, torch::Tensor> reduce_by_index(
                         u_dev.data_ptr<int>(), ugrads.data_ptr<float>(),
                         (u64*)counts.data_ptr<i64>(), cur_stream());
     return {ugrads, counts};
+}
+
+// reduce_by_index followed by apply_optimizer on its result, as one launch:
+// the per-unique sums are applied to the rows behind ``slots`` (int64 [n],
+// saved from the pull) where they are formed. uids at and beyond *u_dev and
+// slots < 0 are skipped.
+void reduce_apply_by_index(
+    int64_t opt, torch::Tensor weights, torch::Tensor state,
+    torch::Tensor slots, torch::Tensor seg_off, torch::Tensor seg_cnt,
+    torch::Tensor perm, torch::Tensor long_list, torch::Tensor n_long,
+    torch::Tensor grads, std::vector<double> cfg, torch::Tensor u_dev) {
+    CHECK_GPU(grads); CHECK_CONT(grads);
+    CHECK_GPU(weights); CHECK_CONT(weights);
+    CHECK_GPU(slots); CHECK_CONT(slots);
+    TORCH_CHECK(grads.dtype() == torch::kFloat32 && grads.dim() == 2,
+                "reduce_apply_by_index: grads must be float32 [n, dim]");
+    TORCH_CHECK(weights.dtype() == torch::kFloat32 && weights.dim() == 2,
+                "reduce_apply_by_index: weights must be float32 [R, dim]");
+    TORCH_CHECK(opt >= 0 && opt <= 8, "reduce_apply_by_index: optimizer id");
+    long n = grads.size(0);
+    long dim = grads.size(1);
+    TORCH_CHECK(dim == weights.size(1),
+                "reduce_apply_by_index: grads do not match the table's dim");
+    TORCH_CHECK(dim <= emb_seg_max_dim(),
+                "reduce_apply_by_index: dim above the kernel's ladder");
+    for (const auto* t : {&seg_off, &seg_cnt, &perm, &long_list, &n_long,
+                          &u_dev}) {
+        CHECK_GPU(*t); CHECK_CONT(*t);
+        TORCH_CHECK(t->dtype() == torch::kInt32,
+                    "reduce_apply_by_index: index tensors must be int32");
+    }
+    TORCH_CHECK(seg_off.numel() == n && seg_cnt.numel() == n
+                && perm.numel() == n,
+                "reduce_apply_by_index: index does not match grads");
+    TORCH_CHECK(slots.dtype() == torch::kInt64 && slots.numel() == n,
+                "reduce_apply_by_index: slots must be int64 [n]");
+    TORCH_CHECK(n_long.numel() == 1 && u_dev.numel() == 1);
+    long sd = state.numel() ? state.size(1) : 0;
+    if (sd) {
+        CHECK_GPU(state); CHECK_CONT(state);
+        TORCH_CHECK(state.dtype() == torch::kFloat32
+                    && state.size(0) == weights.size(0),
+                    "reduce_apply_by_index: state must be float32 [R, sd]");
+    }
+    const c10::cuda::CUDAGuard guard(grads.device());
+    float c[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (size_t i = 0; i < cfg.size() && i < 7; ++i) c[i] = (float)cfg[i];
+    emb_reduce_apply_by_index(
+        (int)opt, seg_off.data_ptr<int>(), seg_cnt.data_ptr<int>(),
+        perm.data_ptr<int>(), long_list.data_ptr<int>(),
+        n_long.data_ptr<int>(), long_list.numel(), grads.data_ptr<float>(),
+        n, dim, u_dev.data_ptr<int>(), slots.data_ptr<i64>(),
+        weights.data_ptr<float>(), sd ? state.data_ptr<float>() : nullptr,
+        sd, c, cur_stream());
 }
 
 // ---- multi-hot bags: pooled gather + bag-indirected reduce ------------
@@ -1658,9 +1854,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "seg_cnt, perm, long_list, n_long)",
           pybind11::arg("keys"),
           pybind11::arg("field_offsets") = pybind11::none());
+    m.def("unique_bounded_assign", &unique_bounded_assign,
+          "unique_bounded_indexed stopped after the assign kernel (array "
+          "touch inside it when valid is given); pull_merged continues",
+          pybind11::arg("keys"),
+          pybind11::arg("field_offsets") = pybind11::none(),
+          pybind11::arg("valid") = pybind11::none(),
+          pybind11::arg("shard_num") = 1);
+    m.def("pull_merged", &pull_merged,
+          "inverse + index filing + gather/lazy init in one launch");
     m.def("reduce_by_index", &reduce_by_index,
           "grad reduce-by-key with counts through the inverted index "
           "(segmented, no atomics)");
+    m.def("reduce_apply_by_index", &reduce_apply_by_index,
+          "reduce_by_index + apply_optimizer in one launch: the summed "
+          "rows are applied where they are formed");
     m.def("seg_reduce_threshold", &emb_seg_threshold,
           "list length above which a uid is in long_list");
     m.def("seg_reduce_max_dim", &emb_seg_max_dim,

@@ -293,7 +293,29 @@ __global__ void k_unique_insert(const i64* __restrict__ keys, long n,
 // waits on one round of returning atomics per wave. Offsets therefore do
 // not follow uid order. A first occurrence without a slot (reserved -1,
 // global overflow) is a list of one and files itself in perm here.
-template <bool IDX>
+//
+// TOUCH: a first occurrence also does what k_array_touch does for its key
+// (array tables): slot = key / shard_num with the same guards (key < 0 and
+// slot >= cap give slot -1 and mask 0, which covers the reserved -1), reads
+// and sets valid[slot] and writes slots[uid] / new_mask[uid]. The key and
+// valid[slot] are loaded beside tcount, before the returning atomics, so
+// the touch adds no round trip to the kernel's chain. Entries at and beyond
+// *u_dev are left to the caller's next kernel (k_pull_merged), because the
+// unique count is final only when this kernel has ended.
+struct UTouch {
+    unsigned char* valid;      // [cap] rows that are live
+    long shard_num, cap;
+    i64* slots;                // [n] per uid: table slot, -1 = none
+    unsigned char* new_mask;   // [n] per uid: the row is new
+};
+
+DEV i64 array_slot(i64 key, long shard_num, long cap) {
+    if (key < 0) return -1;     // C++ division would map -1 to slot 0
+    i64 s = shard_num == 1 ? key : key / shard_num;
+    return (s < 0 || s >= cap) ? -1 : s;
+}
+
+template <bool IDX, bool TOUCH = false>
 __global__ void k_unique_assign(const i64* __restrict__ keys, long n,
                                 const int* __restrict__ slot_of,
                                 const unsigned char* __restrict__ is_first,
@@ -302,7 +324,7 @@ __global__ void k_unique_assign(const i64* __restrict__ keys, long n,
                                 int* __restrict__ counter,
                                 i64* __restrict__ inverse,
                                 const i64* __restrict__ foff, int F,
-                                UIdx ix) {
+                                UIdx ix, UTouch tch) {
     // UA_ITERS elements per thread with ONE returning atomic per wave:
     // ballots for all iterations are taken first (independent loads in
     // flight), their popcounts summed, a single atomicAdd reserves the uid
@@ -314,6 +336,8 @@ __global__ void k_unique_assign(const i64* __restrict__ keys, long n,
     long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
     u64 ballots[UA_ITERS];
     int sl[IDX ? UA_ITERS : 1], c[IDX ? UA_ITERS : 1];
+    i64 tkey[TOUCH ? UA_ITERS : 1], tslot[TOUCH ? UA_ITERS : 1];
+    unsigned char twas[TOUCH ? UA_ITERS : 1];
     int total = 0;
     #pragma unroll
     for (int t = 0; t < UA_ITERS; ++t) {
@@ -321,11 +345,29 @@ __global__ void k_unique_assign(const i64* __restrict__ keys, long n,
         // IDX: every element's slot is read beside is_first (both
         // coalesced), so the tcount lookup does not wait for the ballots
         if constexpr (IDX) sl[t] = (i < n) ? slot_of[i] : -1;
+        if constexpr (TOUCH) {
+            // every element's key, coalesced beside slot_of: valid[slot]
+            // is then one dependent load behind the ballots, like tcount
+            tkey[t] = -1;
+            if (i < n) {
+                tkey[t] = keys[i];
+                if (foff) tkey[t] += foff[(int)i % F];
+            }
+        }
         bool first = (i < n) && is_first[i];
         ballots[t] = __ballot(first);
         total += __popcll(ballots[t]);
     }
     if (!total) return;
+    if constexpr (TOUCH) {
+        #pragma unroll
+        for (int t = 0; t < UA_ITERS; ++t)
+            tslot[t] = (ballots[t] >> lane & 1ull)
+                ? array_slot(tkey[t], tch.shard_num, tch.cap) : -1;
+        #pragma unroll
+        for (int t = 0; t < UA_ITERS; ++t)
+            twas[t] = tslot[t] >= 0 ? tch.valid[tslot[t]] : 1;
+    }
     int off = 0, wtot = 0;
     if constexpr (IDX) {
         int ctot = 0;
@@ -357,8 +399,16 @@ __global__ void k_unique_assign(const i64* __restrict__ keys, long n,
         if (b & (1ull << lane)) {
             long i = i0 + t * stride;
             int uid = base + __popcll(b & ((1ull << lane) - 1ull));
-            i64 kin = keys[i];
-            if (foff) kin += foff[(int)i % F];
+            i64 kin;
+            if constexpr (TOUCH) {
+                kin = tkey[t];
+                tch.slots[uid] = tslot[t];
+                tch.new_mask[uid] = !twas[t];
+                if (tslot[t] >= 0) tch.valid[tslot[t]] = 1;
+            } else {
+                kin = keys[i];
+                if (foff) kin += foff[(int)i % F];
+            }
             unique_keys[uid] = kin;
             int s;
             if constexpr (IDX) s = sl[t]; else s = slot_of[i];
@@ -595,6 +645,156 @@ __global__ void k_gather_init(float* __restrict__ weights,
         if (nm[t]) {
             for (long j = lane; j < dim; j += G) {
                 float v = init_value(init_cat, p0, p1, p2, seed, key[t],
+                                     (u64)j);
+                wrow[j] = v;
+                if (out) out[g * dim + j] = v;
+            }
+            if (sd > 0) {
+                float* srow = state + (u64)slot[t] * sd;
+                for (long j = lane; j < sd; j += G)
+                    srow[j] = state_init_row[j];
+            }
+        } else if (out) {
+            for (long j = lane; j < dim; j += G)
+                out[g * dim + j] = wrow[j];
+        }
+    }
+}
+
+// ------------------------------- inverse + index filing + gather, one launch
+// k_unique_inverse and k_gather_init are one dependent chain (slot_of -> tv
+// -> slots -> new_mask -> row) cut by a launch and a round trip of
+// ``inverse`` through memory; k_pull_merged walks it in one kernel, after
+// the dedup form that stops at k_unique_assign. A G-lane group per element,
+// GI_ILP elements in flight, as k_gather_init:
+//   - the group resolves slot_of[g] -> tv[s] (the uid) with the encodings of
+//     k_unique_inverse: -1 = the assign kernel stored inverse[g] itself,
+//     <= -2 = the duplicate of such an element, which reads the winner's;
+//   - lane 0 stores inverse[g] and perm[toff[s] + rank[g]] = g: stores only,
+//     nothing waits for them;
+//   - the element's key is its own input (keys[g] + foff[g % F]), not
+//     unique_keys[uid];
+//   - the table slot is a policy. SlotArray: straight from the own key
+//     (array_slot, the guards of k_array_touch), so the row load does not
+//     wait for new_mask[uid] and is discarded for a new row. SlotMap: through
+//     slots[uid] (hash tables, after k_ht_lookup);
+//   - then k_gather_init's body: a new row is initialised by every duplicate
+//     with the same deterministic bytes, state rows from state_init_row,
+//     ``out`` optional, slot < 0 reads as zeros.
+// A uid outside [0, min(*u_dev, n)) (only an inconsistent scratch table can
+// give one) is dropped: nothing is read or written for it. SlotArray also
+// writes the tail of slots / new_mask at and beyond *u_dev (-1 and 0), which
+// k_array_touch defined and the touch inside k_unique_assign cannot.
+struct SlotArray {
+    long shard_num, cap;
+    i64* slots_tail;               // [n] tail written here
+    unsigned char* mask_tail;
+    static constexpr bool kTail = true;
+    __device__ __forceinline__ i64 of(i64 key, long) const {
+        return array_slot(key, shard_num, cap);
+    }
+};
+struct SlotMap {
+    const i64* slots;              // [n] per uid
+    static constexpr bool kTail = false;
+    __device__ __forceinline__ i64 of(i64, long uid) const {
+        return slots[uid];
+    }
+};
+
+template <int G, typename Slot>
+__global__ void k_pull_merged(float* __restrict__ weights,
+                              float* __restrict__ state, long dim, long sd,
+                              const i64* __restrict__ keys,
+                              const i64* __restrict__ foff, int F, long n,
+                              const int* __restrict__ slot_of,
+                              const int* __restrict__ tv,
+                              const int* __restrict__ toff,
+                              const int* __restrict__ rank,
+                              i64* __restrict__ inverse,
+                              int* __restrict__ perm,
+                              const unsigned char* __restrict__ new_mask,
+                              Slot sp, float* __restrict__ out,
+                              int init_cat, float p0, float p1, float p2,
+                              u64 seed,
+                              const float* __restrict__ state_init_row,
+                              const int* __restrict__ u_dev) {
+    const long nthreads = (long)gridDim.x * blockDim.x;
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long stride = nthreads / G;
+    const long g0 = tid / G;
+    const int lane = threadIdx.x % G;
+    long live = *u_dev;
+    live = live < 0 ? 0 : (live > n ? n : live);
+    if constexpr (Slot::kTail) {
+        for (long i = live + tid; i < n; i += nthreads) {
+            sp.slots_tail[i] = -1;
+            sp.mask_tail[i] = 0;
+        }
+    }
+
+    int s[GI_ILP];
+    i64 key[GI_ILP];
+    #pragma unroll
+    for (int t = 0; t < GI_ILP; ++t) {
+        long g = g0 + t * stride;
+        s[t] = 0;
+        key[t] = 0;
+        if (g < n) {
+            s[t] = slot_of[g];
+            key[t] = keys[g];
+            if (foff) key[t] += foff[(int)g % F];
+        }
+    }
+    long uid[GI_ILP];
+    int o[GI_ILP], r[GI_ILP];
+    #pragma unroll
+    for (int t = 0; t < GI_ILP; ++t) {
+        long g = g0 + t * stride;
+        uid[t] = -1;
+        o[t] = 0;
+        r[t] = 0;
+        if (g >= n) continue;
+        if (s[t] >= 0) {
+            uid[t] = tv[s[t]];
+            o[t] = toff[s[t]];
+            r[t] = rank[g];
+        } else if (s[t] == -1) {
+            uid[t] = inverse[g];
+        } else {
+            long wnr = -2 - (long)s[t];
+            uid[t] = wnr < n ? inverse[wnr] : -1;
+        }
+    }
+    i64 slot[GI_ILP];
+    unsigned char nm[GI_ILP];
+    #pragma unroll
+    for (int t = 0; t < GI_ILP; ++t) {
+        long g = g0 + t * stride;
+        if (uid[t] >= live) uid[t] = -1;
+        if (uid[t] < 0) { slot[t] = -1; nm[t] = 0; continue; }
+        if (lane == 0) {
+            if (s[t] != -1) inverse[g] = (i64)uid[t];
+            long p = (long)o[t] + r[t];
+            if (s[t] >= 0 && p >= 0 && p < n) perm[p] = (int)g;
+        }
+        slot[t] = sp.of(key[t], uid[t]);
+        nm[t] = new_mask[uid[t]];
+    }
+    #pragma unroll
+    for (int t = 0; t < GI_ILP; ++t) {
+        long g = g0 + t * stride;
+        if (uid[t] < 0)
+            continue;
+        if (slot[t] < 0) {  // no row: zeros out
+            if (out)
+                for (long j = lane; j < dim; j += G) out[g * dim + j] = 0.0f;
+            continue;
+        }
+        float* wrow = weights + (u64)slot[t] * dim;
+        if (nm[t]) {
+            for (long j = lane; j < dim; j += G) {
+                float v = init_value(init_cat, p0, p1, p2, seed, (u64)key[t],
                                      (u64)j);
                 wrow[j] = v;
                 if (out) out[g * dim + j] = v;
@@ -1644,6 +1844,133 @@ enum {
     OPT_ADAMAX = 4, OPT_FTRL = 5, OPT_RMSPROP = 6, OPT_SGD = 7, OPT_TEST = 8
 };
 
+// The formulas exist once: opt_head does the row's scalar state (lane 0 of
+// the group, broadcast with __shfl; the whole G-lane group must be active)
+// and opt_col updates one column from its gradient gj, which k_apply_opt
+// reads from memory and k_seg_reduce_apply holds in a register. ``head`` is
+// what opt_head returned (adam/adamax lr_t, test s0), ``cnt`` the row's
+// occurrence count (test only).
+
+template <int G, int OPT>
+DEV float opt_head(float* s, long dim, int lane, float c0,
+                   float c1, float c2) {
+    if (OPT == OPT_ADAM) {
+        const float lr = c0, b1 = c1, b2 = c2;
+        float lr_t = 0.0f;
+        if (lane == 0) {
+            float b1t = s[2 * dim] * b1;
+            float b2t = s[2 * dim + 1] * b2;
+            s[2 * dim] = b1t;
+            s[2 * dim + 1] = b2t;
+            lr_t = lr * sqrtf(1.0f - b2t) / (1.0f - b1t);
+        }
+        return __shfl(lr_t, 0, G);
+    } else if (OPT == OPT_ADAMAX) {
+        const float lr = c0, b1 = c1;
+        float lr_t = 0.0f;
+        if (lane == 0) {
+            float b1t = s[2 * dim] * b1;
+            s[2 * dim] = b1t;
+            lr_t = lr / (1.0f - b1t);
+        }
+        return __shfl(lr_t, 0, G);
+    } else if (OPT == OPT_TEST) {
+        const float flip = c1;
+        float s0 = 0.0f;
+        if (lane == 0) {
+            s0 = flip - s[0];
+            s[0] = s0;
+        }
+        return __shfl(s0, 0, G);
+    }
+    return 0.0f;
+}
+
+template <int OPT>
+DEV void opt_col(float* w, float* s, long dim,
+                 long j, float gj, float head, float cnt, float c0, float c1,
+                 float c2, float c3, float c4, float c5, float c6) {
+    if (OPT == OPT_DEFAULT) {
+        const float lr = c0;
+        w[j] -= lr * gj;
+    } else if (OPT == OPT_ADADELTA) {
+        const float lr = c0, rho = c1, eps = c2;
+        float* accum = s;
+        float* au = s + dim;
+        float a = accum[j] * rho + gj * gj * (1.0f - rho);
+        accum[j] = a;
+        float upd = gj * sqrtf(au[j] + eps) / sqrtf(a + eps);
+        au[j] = au[j] * rho + upd * upd * (1.0f - rho);
+        w[j] -= lr * upd;
+    } else if (OPT == OPT_ADAGRAD) {
+        const float lr = c0, eps = c2;
+        float* accum = s;
+        float a = accum[j] + gj * gj;
+        accum[j] = a;
+        w[j] -= lr * gj / (sqrtf(a) + eps);
+    } else if (OPT == OPT_ADAM) {
+        const float b1 = c1, b2 = c2, eps = c3;
+        float* m = s;
+        float* v = s + dim;
+        const float lr_t = head;
+        float mj = m[j] * b1 + gj * (1.0f - b1);
+        float vj = v[j] * b2 + gj * gj * (1.0f - b2);
+        m[j] = mj; v[j] = vj;
+        w[j] -= lr_t * mj / (sqrtf(vj) + eps);
+    } else if (OPT == OPT_ADAMAX) {
+        const float b1 = c1, b2 = c2, eps = c3;
+        float* m = s;
+        float* v = s + dim;
+        const float lr_t = head;
+        float mj = m[j] * b1 + gj * (1.0f - b1);
+        float vj = fmaxf(fabsf(gj), v[j] * b2);
+        m[j] = mj; v[j] = vj;
+        w[j] -= lr_t * mj / (vj + eps);
+    } else if (OPT == OPT_FTRL) {
+        const float lr = c0, l1 = c1, l2 = c2, l2s = c3, lrp = c4, beta = c5;
+        float* accum = s;
+        float* linear = s + dim;
+        const float adj_l2 = l2 + beta / lr / 2.0f;
+        float wj = w[j];
+        float gg = gj + 2.0f * l2s * wj;
+        float a_old = accum[j];
+        float a_new = a_old + gj * gj;
+        float sigma, quad;
+        if (lrp == -0.5f) {
+            sigma = (sqrtf(a_new) - sqrtf(a_old)) / lr;
+            quad = sqrtf(a_new) / lr + 2.0f * adj_l2;
+        } else {
+            float p = -lrp;
+            sigma = (powf(a_new, p) - powf(a_old, p)) / lr;
+            quad = powf(a_new, p) / lr + 2.0f * adj_l2;
+        }
+        float lin = linear[j] + gg - sigma * wj;
+        linear[j] = lin;
+        accum[j] = a_new;
+        float l1a = fminf(fmaxf(lin, -l1), l1);
+        w[j] = (l1a - lin) / quad;
+    } else if (OPT == OPT_RMSPROP) {
+        const float lr = c0, rho = c1, mom = c2, eps = c3;
+        float* accum = s;
+        float* moment = s + dim;
+        float a = accum[j] * rho + gj * gj * (1.0f - rho);
+        accum[j] = a;
+        float mo = moment[j] * mom + lr * gj / sqrtf(a + eps);
+        moment[j] = mo;
+        w[j] -= mo;
+    } else if (OPT == OPT_SGD) {
+        const float lr = c0, mom = c1;
+        const bool nesterov = c2 != 0.0f;
+        float* moment = s;
+        float mo = moment[j] * mom + lr * gj;
+        moment[j] = mo;
+        w[j] -= nesterov ? (mo * mom + lr * gj) : mo;
+    } else if (OPT == OPT_TEST) {
+        const float lr = c0, s0 = head;
+        w[j] += lr * gj / cnt + s0;
+    }
+}
+
 template <int G, int OPT>
 __global__ void k_apply_opt(float* __restrict__ weights,
                             float* __restrict__ state,
@@ -1664,128 +1991,186 @@ __global__ void k_apply_opt(float* __restrict__ weights,
     float* s = state + (u64)slot * sd;
     const float* gr = grads + (u64)g * dim;
 
-    if (OPT == OPT_DEFAULT) {
-        const float lr = c0;
-        if (lr != 0.0f)
-            for (long j = lane; j < dim; j += G) w[j] -= lr * gr[j];
-    } else if (OPT == OPT_ADADELTA) {
-        const float lr = c0, rho = c1, eps = c2;
-        float* accum = s;
-        float* au = s + dim;
-        for (long j = lane; j < dim; j += G) {
-            float gj = gr[j];
-            float a = accum[j] * rho + gj * gj * (1.0f - rho);
-            accum[j] = a;
-            float upd = gj * sqrtf(au[j] + eps) / sqrtf(a + eps);
-            au[j] = au[j] * rho + upd * upd * (1.0f - rho);
-            w[j] -= lr * upd;
-        }
-    } else if (OPT == OPT_ADAGRAD) {
-        const float lr = c0, eps = c2;
-        float* accum = s;
-        for (long j = lane; j < dim; j += G) {
-            float gj = gr[j];
-            float a = accum[j] + gj * gj;
-            accum[j] = a;
-            w[j] -= lr * gj / (sqrtf(a) + eps);
-        }
-    } else if (OPT == OPT_ADAM) {
-        const float lr = c0, b1 = c1, b2 = c2, eps = c3;
-        float* m = s;
-        float* v = s + dim;
-        float lr_t = 0.0f;
-        if (lane == 0) {
-            float b1t = s[2 * dim] * b1;
-            float b2t = s[2 * dim + 1] * b2;
-            s[2 * dim] = b1t;
-            s[2 * dim + 1] = b2t;
-            lr_t = lr * sqrtf(1.0f - b2t) / (1.0f - b1t);
-        }
-        lr_t = __shfl(lr_t, 0, G);
-        for (long j = lane; j < dim; j += G) {
-            float gj = gr[j];
-            float mj = m[j] * b1 + gj * (1.0f - b1);
-            float vj = v[j] * b2 + gj * gj * (1.0f - b2);
-            m[j] = mj; v[j] = vj;
-            w[j] -= lr_t * mj / (sqrtf(vj) + eps);
-        }
-    } else if (OPT == OPT_ADAMAX) {
-        const float lr = c0, b1 = c1, b2 = c2, eps = c3;
-        float* m = s;
-        float* v = s + dim;
-        float lr_t = 0.0f;
-        if (lane == 0) {
-            float b1t = s[2 * dim] * b1;
-            s[2 * dim] = b1t;
-            lr_t = lr / (1.0f - b1t);
-        }
-        lr_t = __shfl(lr_t, 0, G);
-        for (long j = lane; j < dim; j += G) {
-            float gj = gr[j];
-            float mj = m[j] * b1 + gj * (1.0f - b1);
-            float vj = fmaxf(fabsf(gj), v[j] * b2);
-            m[j] = mj; v[j] = vj;
-            w[j] -= lr_t * mj / (vj + eps);
-        }
-    } else if (OPT == OPT_FTRL) {
-        const float lr = c0, l1 = c1, l2 = c2, l2s = c3, lrp = c4, beta = c5;
-        float* accum = s;
-        float* linear = s + dim;
-        const float adj_l2 = l2 + beta / lr / 2.0f;
-        for (long j = lane; j < dim; j += G) {
-            float gj = gr[j];
-            float wj = w[j];
-            float gg = gj + 2.0f * l2s * wj;
-            float a_old = accum[j];
-            float a_new = a_old + gj * gj;
-            float sigma, quad;
-            if (lrp == -0.5f) {
-                sigma = (sqrtf(a_new) - sqrtf(a_old)) / lr;
-                quad = sqrtf(a_new) / lr + 2.0f * adj_l2;
-            } else {
-                float p = -lrp;
-                sigma = (powf(a_new, p) - powf(a_old, p)) / lr;
-                quad = powf(a_new, p) / lr + 2.0f * adj_l2;
+    if (OPT == OPT_DEFAULT && c0 == 0.0f) return;   // lr 0: rows untouched
+    const float head = opt_head<G, OPT>(s, dim, lane, c0, c1, c2);
+    const float cnt = OPT == OPT_TEST ? (float)counts[g] : 0.0f;
+    for (long j = lane; j < dim; j += G)
+        opt_col<OPT>(w, s, dim, j, gr[j], head, cnt, c0, c1, c2, c3, c4, c5,
+                     c6);
+}
+
+// ---------------------------------- segmented reduce + optimizer, one launch
+// k_seg_reduce's two roles with the optimizer step in place of the ugrads
+// and counts stores: the lane group (short role) or block (long role) that
+// summed a uid's row applies it to the table row behind slots[uid], so the
+// [n, dim] per-unique gradients and their counts never exist in memory and
+// the commit needs no launch of its own. Same walk, same sum order, same
+// guards as k_seg_reduce, and the same opt_head / opt_col as k_apply_opt:
+// the table afterwards is bit for bit what the two launches leave when the
+// sums do not depend on arrival order. uids at and beyond *u_dev and uids
+// with slot < 0 are skipped, like k_apply_opt skips them; the count the
+// ``test`` optimizer divides by is the clamped seg_cnt. Every live uid is
+// applied exactly once: by the role its clamped count selects.
+template <int G, int CF, int OPT>
+__global__ __launch_bounds__(SEG_BLOCK)
+void k_seg_reduce_apply(const int* __restrict__ seg_off,
+                        const int* __restrict__ seg_cnt,
+                        const int* __restrict__ perm,
+                        const int* __restrict__ long_list,
+                        const int* __restrict__ n_long, long long_cap,
+                        int long_blocks, const float* __restrict__ grads,
+                        long n, long dim, const int* __restrict__ u_dev,
+                        const i64* __restrict__ slots,
+                        float* __restrict__ weights,
+                        float* __restrict__ state, long sd,
+                        float c0, float c1, float c2, float c3, float c4,
+                        float c5, float c6) {
+    __shared__ float red[SEG_BLOCK / 64][G * CF];
+    __shared__ float tot[G * CF];
+    const int lane = threadIdx.x % G;
+    long u = *u_dev;
+    u = u < 0 ? 0 : (u > n ? n : u);
+    if (OPT == OPT_DEFAULT && c0 == 0.0f) return;   // lr 0: rows untouched
+
+    if ((int)blockIdx.x < long_blocks) {
+        // ---- long role
+        long nl = *n_long;
+        nl = nl < 0 ? 0 : (nl > long_cap ? long_cap : nl);
+        const int group = threadIdx.x / G;
+        constexpr int NG = SEG_BLOCK / G;
+        for (long b = blockIdx.x; b < nl; b += long_blocks) {
+            const int uid = long_list[b];
+            int off = 0, cnt = 0;
+            i64 slot = -1;
+            if (uid >= 0 && uid < u) {
+                seg_range(seg_off, seg_cnt, uid, n, off, cnt);
+                slot = slots[uid];
             }
-            float lin = linear[j] + gg - sigma * wj;
-            linear[j] = lin;
-            accum[j] = a_new;
-            float l1a = fminf(fmaxf(lin, -l1), l1);
-            w[j] = (l1a - lin) / quad;
+            if (cnt <= SEG_T) continue;   // block-uniform: the short role's
+            float acc[CF];
+            #pragma unroll
+            for (int c = 0; c < CF; ++c) acc[c] = 0.0f;
+            int e[LR_ILP], en[LR_ILP];
+            #pragma unroll
+            for (int t = 0; t < LR_ILP; ++t)
+                en[t] = (group * LR_ILP + t < cnt)
+                            ? perm[off + group * LR_ILP + t] : -1;
+            for (long base = group * LR_ILP; base < cnt;
+                 base += NG * LR_ILP) {
+                #pragma unroll
+                for (int t = 0; t < LR_ILP; ++t) {
+                    e[t] = (en[t] < 0 || en[t] >= n) ? -1 : en[t];
+                    const long nx = base + NG * LR_ILP + t;
+                    en[t] = (nx < cnt) ? perm[off + nx] : -1;
+                }
+                float v[LR_ILP][CF];
+                #pragma unroll
+                for (int t = 0; t < LR_ILP; ++t)
+                    #pragma unroll
+                    for (int c = 0; c < CF; ++c)
+                        v[t][c] = (e[t] >= 0 && lane + c * G < dim)
+                            ? grads[(u64)e[t] * dim + lane + c * G] : 0.0f;
+                #pragma unroll
+                for (int t = 0; t < LR_ILP; ++t)
+                    #pragma unroll
+                    for (int c = 0; c < CF; ++c) acc[c] += v[t][c];
+            }
+            #pragma unroll
+            for (int d = G; d < 64; d <<= 1)
+                #pragma unroll
+                for (int c = 0; c < CF; ++c)
+                    acc[c] += __shfl_xor(acc[c], d, 64);
+            if ((threadIdx.x & 63) < G) {
+                #pragma unroll
+                for (int c = 0; c < CF; ++c)
+                    red[threadIdx.x / 64][lane + c * G] = acc[c];
+            }
+            __syncthreads();
+            if (threadIdx.x < G * CF) {
+                float s = 0.0f;
+                #pragma unroll
+                for (int w = 0; w < SEG_BLOCK / 64; ++w)
+                    s += red[w][threadIdx.x];
+                tot[threadIdx.x] = s;
+            }
+            __syncthreads();
+            // the block's first group applies the row (slot: block-uniform)
+            if (threadIdx.x < G && slot >= 0) {
+                float* w = weights + (u64)slot * dim;
+                float* s = state + (u64)slot * sd;
+                const float head = opt_head<G, OPT>(s, dim, lane, c0, c1, c2);
+                #pragma unroll
+                for (int c = 0; c < CF; ++c)
+                    if (lane + c * G < dim)
+                        opt_col<OPT>(w, s, dim, lane + c * G,
+                                     tot[lane + c * G], head, (float)cnt, c0,
+                                     c1, c2, c3, c4, c5, c6);
+            }
         }
-    } else if (OPT == OPT_RMSPROP) {
-        const float lr = c0, rho = c1, mom = c2, eps = c3;
-        float* accum = s;
-        float* moment = s + dim;
-        for (long j = lane; j < dim; j += G) {
-            float gj = gr[j];
-            float a = accum[j] * rho + gj * gj * (1.0f - rho);
-            accum[j] = a;
-            float mo = moment[j] * mom + lr * gj / sqrtf(a + eps);
-            moment[j] = mo;
-            w[j] -= mo;
+        return;
+    }
+
+    // ---- short role
+    const long ngroups = (long)(gridDim.x - long_blocks) * (SEG_BLOCK / G);
+    const long g0 = ((long)(blockIdx.x - long_blocks) * SEG_BLOCK
+                     + threadIdx.x) / G;
+    int off[SR_ILP], cnt[SR_ILP], e0[SR_ILP];
+    i64 slot[SR_ILP];
+    #pragma unroll
+    for (int t = 0; t < SR_ILP; ++t) {
+        long uid = g0 + t * ngroups;
+        off[t] = 0;
+        cnt[t] = 0;
+        slot[t] = -1;
+        if (uid < u) {
+            seg_range(seg_off, seg_cnt, uid, n, off[t], cnt[t]);
+            slot[t] = slots[uid];   // with the range, not behind the chain
         }
-    } else if (OPT == OPT_SGD) {
-        const float lr = c0, mom = c1;
-        const bool nesterov = c2 != 0.0f;
-        float* moment = s;
-        for (long j = lane; j < dim; j += G) {
-            float gj = gr[j];
-            float mo = moment[j] * mom + lr * gj;
-            moment[j] = mo;
-            w[j] -= nesterov ? (mo * mom + lr * gj) : mo;
+    }
+    #pragma unroll
+    for (int t = 0; t < SR_ILP; ++t) {
+        e0[t] = (cnt[t] > 0 && cnt[t] <= SEG_T) ? perm[off[t]] : -1;
+        if (e0[t] < 0 || e0[t] >= n) e0[t] = -1;
+    }
+    float acc[SR_ILP][CF];
+    #pragma unroll
+    for (int t = 0; t < SR_ILP; ++t)
+        #pragma unroll
+        for (int c = 0; c < CF; ++c)
+            acc[t][c] = (e0[t] >= 0 && lane + c * G < dim)
+                ? grads[(u64)e0[t] * dim + lane + c * G] : 0.0f;
+    #pragma unroll
+    for (int t = 0; t < SR_ILP; ++t) {
+        long uid = g0 + t * ngroups;
+        if (uid >= u || cnt[t] > SEG_T) continue;   // none / the long role's
+        for (int k = 1; k < cnt[t]; k += SR_ILP) {
+            int e[SR_ILP];
+            #pragma unroll
+            for (int q = 0; q < SR_ILP; ++q) {
+                e[q] = (k + q < cnt[t]) ? perm[off[t] + k + q] : -1;
+                if (e[q] < 0 || e[q] >= n) e[q] = -1;
+            }
+            float v[SR_ILP][CF];
+            #pragma unroll
+            for (int q = 0; q < SR_ILP; ++q)
+                #pragma unroll
+                for (int c = 0; c < CF; ++c)
+                    v[q][c] = (e[q] >= 0 && lane + c * G < dim)
+                        ? grads[(u64)e[q] * dim + lane + c * G] : 0.0f;
+            #pragma unroll
+            for (int q = 0; q < SR_ILP; ++q)
+                #pragma unroll
+                for (int c = 0; c < CF; ++c) acc[t][c] += v[q][c];
         }
-    } else if (OPT == OPT_TEST) {
-        const float lr = c0, flip = c1;
-        float s0 = 0.0f;
-        if (lane == 0) {
-            s0 = flip - s[0];
-            s[0] = s0;
-        }
-        s0 = __shfl(s0, 0, G);
-        float cnt = (float)counts[g];
-        for (long j = lane; j < dim; j += G)
-            w[j] += lr * gr[j] / cnt + s0;
+        if (slot[t] < 0) continue;
+        float* w = weights + (u64)slot[t] * dim;
+        float* s = state + (u64)slot[t] * sd;
+        const float head = opt_head<G, OPT>(s, dim, lane, c0, c1, c2);
+        #pragma unroll
+        for (int c = 0; c < CF; ++c)
+            if (lane + c * G < dim)
+                opt_col<OPT>(w, s, dim, lane + c * G, acc[t][c], head,
+                             (float)cnt[t], c0, c1, c2, c3, c4, c5, c6);
     }
 }
 
@@ -2492,12 +2877,15 @@ static void gather_lookup_q_fmt(const unsigned int* slab, long dim, long n,
 #undef LAUNCH_GATHER_Q
 }
 
+// ``tch`` non-null is the form that stops after assign (with the array
+// touch inside it when tch->valid is set): the caller's k_pull_merged
+// resolves slot_of -> tv itself and files the elements.
 template <bool IDX>
 static void unique_launch(const i64* keys, long n, u64* tk, int* tv, long cap,
                           int* slot_of, unsigned char* is_first,
                           i64* unique_keys, i64* inverse, int* counter,
                           const i64* foff, int F, const UIdx& ix,
-                          hipStream_t stream) {
+                          hipStream_t stream, const UTouch* tch = nullptr) {
     // fill kernel, not hipMemsetAsync: memsets issued here were NOT
     // replayed inside hipGraph captures (scratch kept stale keys across
     // replays until the probe loops hung); kernels always capture. One
@@ -2513,9 +2901,20 @@ static void unique_launch(const i64* keys, long n, u64* tk, int* tv, long cap,
         keys, n, tk, mask, slot_of, is_first, foff, F, ix);
     int ga = grid1d((n + UA_ITERS - 1) / UA_ITERS);
     int gi = grid1d((n + UI_ILP - 1) / UI_ILP);
+    if (tch) {
+        if (IDX && tch->valid)
+            k_unique_assign<IDX, IDX><<<ga, BLOCK, 0, stream>>>(
+                keys, n, slot_of, is_first, tv, unique_keys, counter,
+                inverse, foff, F, ix, *tch);
+        else
+            k_unique_assign<IDX><<<ga, BLOCK, 0, stream>>>(
+                keys, n, slot_of, is_first, tv, unique_keys, counter,
+                inverse, foff, F, ix, UTouch{});
+        return;
+    }
     k_unique_assign<IDX><<<ga, BLOCK, 0, stream>>>(
         keys, n, slot_of, is_first, tv, unique_keys, counter, inverse, foff,
-        F, ix);
+        F, ix, UTouch{});
     k_unique_inverse<IDX><<<gi, BLOCK, 0, stream>>>(n, slot_of, tv, inverse,
                                                     ix);
 }
@@ -2546,6 +2945,59 @@ void emb_unique_indexed(const i64* keys, long n, u64* tk, int* tv, long cap,
             off_counter, n_long, long_cap};
     unique_launch<true>(keys, n, tk, tv, cap, slot_of, is_first, unique_keys,
                         inverse, counter, foff, F, ix, stream);
+}
+
+// emb_unique_indexed without its last kernel, for k_pull_merged: stops
+// after k_unique_assign, which also touches the array table when ``valid``
+// is given (slots / new_mask [n] per uid; their tail is emb_pull_merged's).
+// slot_of, tv, toff and rank are then the merged kernel's inputs; inverse
+// holds only the entries the assign kernel stores itself.
+void emb_unique_indexed_assign(const i64* keys, long n, u64* tk, int* tv,
+                               long cap, int* slot_of,
+                               unsigned char* is_first, i64* unique_keys,
+                               i64* inverse, int* counter, const i64* foff,
+                               int F, int* tcount, int* toff, int* rank,
+                               int* seg_off, int* seg_cnt, int* perm,
+                               int* long_list, long long_cap,
+                               int* off_counter, int* n_long,
+                               unsigned char* valid, long shard_num,
+                               long table_cap, i64* slots,
+                               unsigned char* new_mask, hipStream_t stream) {
+    UIdx ix{tcount, toff, rank, seg_off, seg_cnt, perm, long_list,
+            off_counter, n_long, long_cap};
+    UTouch tch{valid, shard_num, table_cap, slots, new_mask};
+    unique_launch<true>(keys, n, tk, tv, cap, slot_of, is_first, unique_keys,
+                        inverse, counter, foff, F, ix, stream, &tch);
+}
+
+// The rest of the pull after emb_unique_indexed_assign (and, for hash
+// tables, emb_ht_lookup): inverse, the index's perm and gather/init in one
+// launch. ``array`` != 0 takes the slot from the element's own key and
+// writes the tail of slots / new_mask; otherwise slots [n] is read per uid.
+void emb_pull_merged(float* weights, float* state, long dim, long sd,
+                     const i64* keys, const i64* foff, int F, long n,
+                     const int* slot_of, const int* tv, const int* toff,
+                     const int* rank, i64* inverse, int* perm, i64* slots,
+                     unsigned char* new_mask, int array, long shard_num,
+                     long table_cap, float* out, int init_cat, float p0,
+                     float p1, float p2, u64 seed,
+                     const float* state_init_row, const int* u_dev,
+                     hipStream_t stream) {
+    if (n == 0) return;
+    long npg = (n + GI_ILP - 1) / GI_ILP;
+#define LAUNCH_PM(G, SP)                                                    \
+    k_pull_merged<G><<<grid1d(npg * G), BLOCK, 0, stream>>>(                \
+        weights, state, dim, sd, keys, foff, F, n, slot_of, tv, toff, rank, \
+        inverse, perm, new_mask, SP, out, init_cat, p0, p1, p2, seed,       \
+        state_init_row, u_dev)
+    if (array) {
+        SlotArray sp{shard_num, table_cap, slots, new_mask};
+        if (dim <= 32) LAUNCH_PM(16, sp); else LAUNCH_PM(64, sp);
+    } else {
+        SlotMap sp{slots};
+        if (dim <= 32) LAUNCH_PM(16, sp); else LAUNCH_PM(64, sp);
+    }
+#undef LAUNCH_PM
 }
 
 int emb_seg_threshold() { return SEG_T; }
@@ -2847,6 +3299,46 @@ void emb_apply_optimizer(int opt, float* weights, float* state, long dim,
         }
         (void)G;
     }
+}
+
+// emb_reduce_by_index + emb_apply_optimizer in one launch: nothing per
+// unique leaves the kernel but the table rows. dim <= SEG_MAX_DIM (the
+// caller checks); an unknown ``opt`` launches nothing.
+void emb_reduce_apply_by_index(int opt, const int* seg_off,
+                               const int* seg_cnt, const int* perm,
+                               const int* long_list, const int* n_long,
+                               long long_cap, const float* grads, long n,
+                               long dim, const int* u_dev, const i64* slots,
+                               float* weights, float* state, long sd,
+                               const float* c, hipStream_t stream) {
+    if (n == 0) return;
+    int lb = (int)(long_cap < SEG_LONG_BLOCKS ? long_cap : SEG_LONG_BLOCKS);
+    long groups = (n + SR_ILP - 1) / SR_ILP;
+#define LAUNCH_SEG_OPT(G, CF, OPT)                                          \
+    k_seg_reduce_apply<G, CF, OPT>                                          \
+        <<<lb + cdiv(groups * G, SEG_BLOCK), SEG_BLOCK, 0, stream>>>(       \
+            seg_off, seg_cnt, perm, long_list, n_long, long_cap, lb, grads, \
+            n, dim, u_dev, slots, weights, state, sd, c[0], c[1], c[2],     \
+            c[3], c[4], c[5], c[6])
+#define SWITCH_SEG_OPT(G, CF)                                               \
+    switch (opt) {                                                          \
+        case OPT_DEFAULT: LAUNCH_SEG_OPT(G, CF, OPT_DEFAULT); break;        \
+        case OPT_ADADELTA: LAUNCH_SEG_OPT(G, CF, OPT_ADADELTA); break;      \
+        case OPT_ADAGRAD: LAUNCH_SEG_OPT(G, CF, OPT_ADAGRAD); break;        \
+        case OPT_ADAM: LAUNCH_SEG_OPT(G, CF, OPT_ADAM); break;              \
+        case OPT_ADAMAX: LAUNCH_SEG_OPT(G, CF, OPT_ADAMAX); break;          \
+        case OPT_FTRL: LAUNCH_SEG_OPT(G, CF, OPT_FTRL); break;              \
+        case OPT_RMSPROP: LAUNCH_SEG_OPT(G, CF, OPT_RMSPROP); break;        \
+        case OPT_SGD: LAUNCH_SEG_OPT(G, CF, OPT_SGD); break;                \
+        case OPT_TEST: LAUNCH_SEG_OPT(G, CF, OPT_TEST); break;              \
+    }
+    // the rungs of emb_reduce_by_index; G is emb_apply_optimizer's too
+    if (dim <= 16) { SWITCH_SEG_OPT(16, 1) }
+    else if (dim <= 32) { SWITCH_SEG_OPT(16, 2) }
+    else if (dim <= 64) { SWITCH_SEG_OPT(64, 1) }
+    else { SWITCH_SEG_OPT(64, 2) }
+#undef SWITCH_SEG_OPT
+#undef LAUNCH_SEG_OPT
 }
 
 void emb_mask_tail(i64* keys, float* grads, u64* counts, long n, long dim,

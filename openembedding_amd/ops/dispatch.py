@@ -99,6 +99,33 @@ def reduce_by_index(index, grads: torch.Tensor, u_dev
     return ugrads, counts
 
 
+def reduce_apply_by_index(opt_id: int, weights: torch.Tensor,
+                          state: torch.Tensor, slots: torch.Tensor, index,
+                          grads: torch.Tensor, cfg, u_dev) -> None:
+    """``reduce_by_index`` and the sparse optimizer step on its result: the
+    rows of ``weights`` / ``state`` behind ``slots`` (int64 [n], -1 = skip)
+    are updated in place from the per-unique sums of ``grads`` [n, dim].
+
+    One launch where ``seg_reduce_covers(grads)``: the sums are applied where
+    they are formed and never written out. Everything else on the GPU (a dim
+    above the ladder) takes the two launches, ``reduce_by_index`` then
+    ``apply_optimizer``. ``opt_id`` / ``cfg`` as ``apply_optimizer`` takes
+    them (core/variable_gpu.py)."""
+    ext = require_hip() if _use_hip(grads) else None
+    if ext is None or weights.dtype != torch.float32:
+        raise NotImplementedError(
+            "reduce_apply_by_index serves float32 GPU tables; other "
+            "variables reduce at push time and commit through their shard")
+    grads = grads.contiguous()
+    if seg_reduce_covers(grads):
+        ext.reduce_apply_by_index(opt_id, weights, state, slots, *index,
+                                  grads, list(cfg), u_dev)
+        return
+    ugrads, counts = reduce_by_index(index, grads, u_dev)
+    ext.apply_optimizer(opt_id, weights, state, slots, ugrads, counts,
+                        list(cfg), u_dev)
+
+
 # ------------------------------------------------------------ multi-hot bags
 
 POOL_MODES = {"sum": 0, "mean": 1, "sqrtn": 2}

@@ -37,6 +37,16 @@ from . import comm
 # embops.hip, "segmented reduce"): on by default; OEAMD_SEG_REDUCE=0 keeps
 # the atomic reduce-by-inverse everywhere (A/B runs, fallback switch).
 _SEG_REDUCE = os.environ.get("OEAMD_SEG_REDUCE", "1") != "0"
+# One launch for the segmented reduce and the optimizer step of the flat
+# local bounded route (embops.hip, "segmented reduce + optimizer"): on by
+# default; OEAMD_FUSED_APPLY=0 reduces at push time and applies at the commit
+# as two launches.
+_FUSED_APPLY = os.environ.get("OEAMD_FUSED_APPLY", "1") != "0"
+# The flat local bounded pull with the array touch inside the dedup's assign
+# kernel and inverse + index filing + gather/init as one kernel (embops.hip,
+# k_pull_merged): on by default; OEAMD_FUSED_PULL=0 keeps k_unique_inverse,
+# k_array_touch and k_gather_init as launches of their own.
+_FUSED_PULL = os.environ.get("OEAMD_FUSED_PULL", "1") != "0"
 
 
 def _unique_bounded(ext, flat: torch.Tensor, field_offsets):
@@ -225,9 +235,14 @@ class ShardedVariable:
         """Single-GPU sync-free pull: bounded unique buffer + fused
         gather/init/scatter; zero host round-trips (hipGraph-capturable)."""
         ext = self.shard.ext
-        uk_buf, inverse, u_dev, index = _unique_bounded(ext, flat,
-                                                        field_offsets)
-        out, slots = self.shard.pull_bounded(uk_buf, u_dev, inverse)
+        if (_FUSED_PULL and _SEG_REDUCE and flat.numel()
+                and getattr(self.shard, "fused_pull", False)):
+            out, uk_buf, inverse, u_dev, index, slots = \
+                self.shard.pull_bounded_fused(flat, field_offsets)
+        else:
+            uk_buf, inverse, u_dev, index = _unique_bounded(ext, flat,
+                                                            field_offsets)
+            out, slots = self.shard.pull_bounded(uk_buf, u_dev, inverse)
         h = PullHandle(shape=indices.shape, unique=uk_buf, inverse=inverse,
                        bounded=True, u_dev=u_dev, slots=slots, index=index)
         return out.view(*indices.shape, self.shard.dim), h
@@ -594,6 +609,14 @@ class ShardedVariable:
         """grads: [*shape, dim] gradient of the pulled weights."""
         dim = self.shard.dim
         g = grads.reshape(-1, dim)
+        if (_FUSED_APPLY and h.index is not None and h.bounded
+                and not h.padded and g.is_contiguous()
+                and getattr(self.shard, "fused_apply", False)
+                and ops.seg_reduce_covers(g)):
+            # flat local bounded route: queue the block unreduced; the
+            # commit sums and applies it in one launch
+            self.shard.push_index(h.unique, h.u_dev, h.slots, g, h.index)
+            return
         if h.index is not None and ops.seg_reduce_covers(g):
             ugrads, counts = ops.reduce_by_index(h.index, g, h.u_dev)
         else:
