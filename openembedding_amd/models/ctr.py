@@ -12,6 +12,7 @@ and return logits [B].
 from __future__ import annotations
 
 import math
+import os
 from typing import List, Optional, Sequence
 
 import torch
@@ -22,10 +23,25 @@ from ..torch import CombinedEmbedding
 from .criteo import CRITEO_FIELD_VOCABS, N_DENSE
 
 
+# Row-staged head kernels and the backward that accumulates into bound
+# grads (docs/kernels.md "ctrhead.hip"): on by default; OEAMD_HEAD_ROWS=0
+# keeps the per-field forward, the bwd_e + bwd_d pair and autograd's
+# AccumulateGrad for dense_linear, in the same build, for A/B runs
+# ("fwd" / "bwd" switch on one half only). Read once at import.
+_HEAD_ROWS_ENV = os.environ.get("OEAMD_HEAD_ROWS", "1")
+_HEAD_ROWS = _HEAD_ROWS_ENV != "0"
+_HEAD_ROWS_FWD = _HEAD_ROWS_ENV not in ("0", "bwd")
+_HEAD_ROWS_BWD = _HEAD_ROWS_ENV not in ("0", "fwd")
+
+
 class _FusedCTRHeadFn(torch.autograd.Function):
     """Fused interaction head (ops/csrc/ctrhead.hip): one kernel assembles
     deep_in (cast fused) and computes first-order + FM + dense-linear
-    partial logits; one kernel does the whole backward. Replaces ~20 small
+    partial logits. Backward: one launch (k_ctr_head_bwd_rows) where the
+    row-staged kernels fit, else the elementwise kernel plus the dense-tail
+    kernel. When dense_linear's .grad tensors are bound (the flat
+    optimizer's fp32 views), dw/db are added into them by the kernel and
+    autograd gets None for both, as in _FusedMLP3Fn. Replaces ~20 small
     elementwise/reduce launches per step (profiles/)."""
 
     @staticmethod
@@ -37,9 +53,10 @@ class _FusedCTRHeadFn(torch.autograd.Function):
         dense = dense.contiguous()
         deep_in, partial, s = ext.ctr_head_fwd(
             e_all, dense, wf, b.reshape(-1).contiguous(), use_fm, out_bf16,
-            pad32)
+            pad32, 0 if _HEAD_ROWS_FWD else 1)
         ctx.save_for_backward(e_all, dense, wf, s)
         ctx.use_fm = use_fm
+        ctx._params = (w, b)
         return deep_in, partial
 
     @staticmethod
@@ -47,9 +64,24 @@ class _FusedCTRHeadFn(torch.autograd.Function):
         from ..ops import require_hip
         ext = require_hip()
         e_all, dense, wf, s = ctx.saved_tensors
+        w, b = ctx._params
+        prebound = _HEAD_ROWS_BWD and all(
+            p.requires_grad and p.grad is not None
+            and p.grad.dtype == torch.float32
+            and p.grad.is_contiguous() and p.grad.device == e_all.device
+            for p in (w, b))
+        if prebound:
+            # 0 + sum with the flat optimizer (k_flat_opt leaves the buffer
+            # zeroed): what AccumulateGrad produced, without its launches
+            de_all, d_dense = ext.ctr_head_bwd_acc(
+                e_all, dense, wf, d_deep_in.contiguous(),
+                d_partial.contiguous(), s, ctx.use_fm, w.grad.view(-1),
+                b.grad.view(-1), ctx.needs_input_grad[1])
+            return de_all, d_dense, None, None, None, None, None
         de_all, d_dense, dw, db = ext.ctr_head_bwd(
             e_all, dense, wf, d_deep_in.contiguous(),
-            d_partial.contiguous(), s, ctx.use_fm)
+            d_partial.contiguous(), s, ctx.use_fm,
+            0 if _HEAD_ROWS_BWD else 1)
         return de_all, d_dense, dw.view(1, -1), db, None, None, None
 
 

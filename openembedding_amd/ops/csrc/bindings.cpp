@@ -101,6 +101,15 @@ void emb_ctr_head_bwd(const float*, const float*, const float*, const void*,
                       const float*, const float*, long, long, long, long,
                       long, float*, float*, float*, float*, int, int,
                       hipStream_t_);
+int emb_ctr_head_rows_waves(long, long, long, long, long, int, int);
+long emb_ctr_head_rows_bwd_grid(long, long, int);
+void emb_ctr_head_fwd_rows(const float*, const float*, const float*,
+                           const float*, long, long, long, long, long, void*,
+                           float*, float*, int, int, int, hipStream_t_);
+void emb_ctr_head_bwd_rows(const float*, const float*, const float*,
+                           const void*, const float*, const float*, long,
+                           long, long, long, long, float*, float*, float*,
+                           float*, int, int, int, hipStream_t_);
 void emb_mlp3_bias_bwd(const float*, const void*, const void*, const void*,
                        const void*, long, long, float*, void*, void*, void*,
                        void*, void*, int, int, hipStream_t_);
@@ -1400,10 +1409,17 @@ void apply_optimizer(int64_t opt, torch::Tensor weights, torch::Tensor state,
 
 // ---- fused CTR interaction head ---------------------------------------
 
+// impl (ctr_head_fwd / ctr_head_bwd): 0 = the launcher's choice, the
+// row-staged kernels where their LDS images fit; 1 = the per-field forward
+// and the bwd_e + bwd_d pair; 2 = row-staged or an error.
+#define CHECK_F32(t) \
+    TORCH_CHECK((t).scalar_type() == torch::kFloat32, #t " must be float32")
+
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ctr_head_fwd(
     torch::Tensor e_all, torch::Tensor dense, torch::Tensor w,
-    torch::Tensor bias, bool use_fm, bool out_bf16, bool pad32) {
+    torch::Tensor bias, bool use_fm, bool out_bf16, bool pad32, int64_t impl) {
     CHECK_GPU(e_all); CHECK_CONT(e_all); CHECK_CONT(dense); CHECK_CONT(w);
+    TORCH_CHECK(impl >= 0 && impl <= 2, "ctr_head: impl must be 0, 1 or 2");
     const c10::cuda::CUDAGuard guard(e_all.device());
     long B = e_all.size(0), F = e_all.size(1), D1 = e_all.size(2);
     long dim = D1 - 1, nd = dense.size(1);
@@ -1413,30 +1429,106 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ctr_head_fwd(
                                                    : torch::kFloat32);
     long width = F * dim + nd;
     long stride = pad32 ? ((width + 31) / 32) * 32 : width;
+    int S = 0;
+    if (impl != 1) {
+        S = emb_ctr_head_rows_waves(B, F, dim, nd, stride, out_bf16 ? 1 : 0,
+                                    0);
+        TORCH_CHECK(S > 0 || impl == 0, "ctr_head_fwd: impl 2, but the "
+                    "row-staged kernel does not fit this shape");
+    }
+    if (S > 0) {
+        CHECK_F32(e_all); CHECK_F32(dense); CHECK_F32(w); CHECK_F32(bias);
+        CHECK_GPU(dense); CHECK_GPU(w); CHECK_GPU(bias);
+        TORCH_CHECK(dense.size(0) == B && w.numel() == nd
+                    && bias.numel() >= 1, "ctr_head_fwd: operand lengths");
+    }
     auto deep_in = torch::empty({B, stride}, out_opts);
     auto partial = torch::empty({B}, e_all.options());
     auto s_out = torch::empty({B, dim}, e_all.options());
     CHECK_CONT(bias);
-    emb_ctr_head_fwd(e_all.data_ptr<float>(), dense.data_ptr<float>(),
-                     w.data_ptr<float>(), bias.data_ptr<float>(), B, F, dim, nd,
-                     stride, deep_in.data_ptr(), partial.data_ptr<float>(),
-                     s_out.data_ptr<float>(),
-                     use_fm ? 1 : 0, out_bf16 ? 1 : 0, cur_stream());
+    if (S > 0)
+        emb_ctr_head_fwd_rows(e_all.data_ptr<float>(),
+                              dense.data_ptr<float>(), w.data_ptr<float>(),
+                              bias.data_ptr<float>(), B, F, dim, nd, stride,
+                              deep_in.data_ptr(), partial.data_ptr<float>(),
+                              s_out.data_ptr<float>(), use_fm ? 1 : 0,
+                              out_bf16 ? 1 : 0, S, cur_stream());
+    else
+        emb_ctr_head_fwd(e_all.data_ptr<float>(), dense.data_ptr<float>(),
+                         w.data_ptr<float>(), bias.data_ptr<float>(), B, F,
+                         dim, nd, stride, deep_in.data_ptr(),
+                         partial.data_ptr<float>(), s_out.data_ptr<float>(),
+                         use_fm ? 1 : 0, out_bf16 ? 1 : 0, cur_stream());
     return {deep_in, partial, s_out};
+}
+
+// shapes and dtypes the merged backward relies on; returns out_bf16
+static bool head_bwd_check(const torch::Tensor& e_all,
+                           const torch::Tensor& dense,
+                           const torch::Tensor& w,
+                           const torch::Tensor& d_deep_in,
+                           const torch::Tensor& d_partial,
+                           const torch::Tensor& s_in) {
+    CHECK_GPU(e_all); CHECK_GPU(dense); CHECK_GPU(w); CHECK_GPU(d_deep_in);
+    CHECK_GPU(d_partial); CHECK_GPU(s_in);
+    CHECK_CONT(e_all); CHECK_CONT(dense); CHECK_CONT(w);
+    CHECK_CONT(d_deep_in); CHECK_CONT(d_partial); CHECK_CONT(s_in);
+    CHECK_F32(e_all); CHECK_F32(dense); CHECK_F32(w); CHECK_F32(d_partial);
+    CHECK_F32(s_in);
+    TORCH_CHECK(e_all.dim() == 3 && dense.dim() == 2 && d_deep_in.dim() == 2,
+                "ctr_head_bwd: e_all [B,F,D1], dense [B,nd], d_deep_in "
+                "[B,stride]");
+    long B = e_all.size(0), F = e_all.size(1), dim = e_all.size(2) - 1;
+    long nd = dense.size(1);
+    bool bf = d_deep_in.scalar_type() == torch::kBFloat16;
+    TORCH_CHECK(bf || d_deep_in.scalar_type() == torch::kFloat32,
+                "ctr_head_bwd: d_deep_in must be bfloat16 or float32");
+    TORCH_CHECK(dense.size(0) == B && w.numel() == nd
+                && d_deep_in.size(0) == B
+                && d_deep_in.size(1) >= F * dim + nd
+                && d_partial.numel() == B && s_in.numel() == B * dim,
+                "ctr_head_bwd: operand lengths");
+    return bf;
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 ctr_head_bwd(torch::Tensor e_all, torch::Tensor dense, torch::Tensor w,
              torch::Tensor d_deep_in, torch::Tensor d_partial,
-             torch::Tensor s_in, bool use_fm) {
+             torch::Tensor s_in, bool use_fm, int64_t impl) {
     CHECK_GPU(e_all); CHECK_CONT(e_all); CHECK_CONT(d_deep_in);
+    TORCH_CHECK(impl >= 0 && impl <= 2, "ctr_head: impl must be 0, 1 or 2");
     const c10::cuda::CUDAGuard guard(e_all.device());
     long B = e_all.size(0), F = e_all.size(1), D1 = e_all.size(2);
     long dim = D1 - 1, nd = dense.size(1);
     long stride = d_deep_in.size(1);  // may be 32-padded
     bool out_bf16 = d_deep_in.dtype() == torch::kBFloat16;
+    int S = 0;
+    if (impl != 1) {
+        S = emb_ctr_head_rows_waves(B, F, dim, nd, stride, out_bf16 ? 1 : 0,
+                                    impl == 0 ? 2 : 1);
+        TORCH_CHECK(S > 0 || impl == 0, "ctr_head_bwd: impl 2, but the "
+                    "row-staged kernel does not fit this shape");
+    }
     auto de_all = torch::empty_like(e_all);
     auto d_dense = torch::empty_like(dense);
+    if (S > 0) {
+        head_bwd_check(e_all, dense, w, d_deep_in, d_partial, s_in);
+        // the merged kernel accumulates: one zero fill for both
+        auto acc = torch::zeros({nd + 1}, w.options());
+        auto dw = acc.narrow(0, 0, nd).view_as(w);
+        auto db = acc.narrow(0, nd, 1);
+        emb_ctr_head_bwd_rows(e_all.data_ptr<float>(),
+                              dense.data_ptr<float>(), w.data_ptr<float>(),
+                              d_deep_in.data_ptr(),
+                              d_partial.data_ptr<float>(),
+                              s_in.data_ptr<float>(), B, F, dim, nd, stride,
+                              de_all.data_ptr<float>(),
+                              d_dense.data_ptr<float>(),
+                              dw.data_ptr<float>(), db.data_ptr<float>(),
+                              use_fm ? 1 : 0, out_bf16 ? 1 : 0, S,
+                              cur_stream());
+        return {de_all, d_dense, dw, db};
+    }
     // dw/db are zeroed by k_ctr_head_bwd_e before bwd_d accumulates
     auto dw = torch::empty_like(w);
     auto db = torch::empty({1}, w.options());
@@ -1449,6 +1541,66 @@ ctr_head_bwd(torch::Tensor e_all, torch::Tensor dense, torch::Tensor w,
                      dw.data_ptr<float>(), db.data_ptr<float>(),
                      use_fm ? 1 : 0, out_bf16 ? 1 : 0, cur_stream());
     return {de_all, d_dense, dw, db};
+}
+
+// Backward that adds dw/db into the caller's buffers (the flat optimizer's
+// bound .grad views): no temporaries, no AccumulateGrad launches. A shape
+// the launcher does not give to the merged kernel (impl 0 of ctr_head_bwd)
+// runs the two-launch pair and adds.
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>>
+ctr_head_bwd_acc(torch::Tensor e_all, torch::Tensor dense, torch::Tensor w,
+                 torch::Tensor d_deep_in, torch::Tensor d_partial,
+                 torch::Tensor s_in, bool use_fm, torch::Tensor dw_acc,
+                 torch::Tensor db_acc, bool want_d_dense) {
+    bool out_bf16 = head_bwd_check(e_all, dense, w, d_deep_in, d_partial,
+                                   s_in);
+    long B = e_all.size(0), F = e_all.size(1), dim = e_all.size(2) - 1;
+    long nd = dense.size(1), stride = d_deep_in.size(1);
+    CHECK_GPU(dw_acc); CHECK_GPU(db_acc); CHECK_CONT(dw_acc);
+    CHECK_CONT(db_acc); CHECK_F32(dw_acc); CHECK_F32(db_acc);
+    TORCH_CHECK(dw_acc.dim() == 1 && dw_acc.numel() == nd,
+                "ctr_head_bwd_acc: dw_acc must be [nd]");
+    TORCH_CHECK(db_acc.dim() == 1 && db_acc.numel() == 1,
+                "ctr_head_bwd_acc: db_acc must be [1]");
+    TORCH_CHECK(dw_acc.device() == e_all.device()
+                && db_acc.device() == e_all.device(),
+                "ctr_head_bwd_acc: accumulators on another device");
+    const c10::cuda::CUDAGuard guard(e_all.device());
+    int S = emb_ctr_head_rows_waves(B, F, dim, nd, stride, out_bf16 ? 1 : 0,
+                                    2);
+    if (S == 0) {
+        auto r = ctr_head_bwd(e_all, dense, w, d_deep_in, d_partial, s_in,
+                              use_fm, 1);
+        dw_acc.add_(std::get<2>(r).reshape(-1));
+        db_acc.add_(std::get<3>(r));
+        if (want_d_dense) return {std::get<0>(r), std::get<1>(r)};
+        return {std::get<0>(r), c10::nullopt};
+    }
+    auto de_all = torch::empty_like(e_all);
+    c10::optional<torch::Tensor> d_dense;
+    if (want_d_dense) d_dense = torch::empty_like(dense);
+    emb_ctr_head_bwd_rows(e_all.data_ptr<float>(), dense.data_ptr<float>(),
+                          w.data_ptr<float>(), d_deep_in.data_ptr(),
+                          d_partial.data_ptr<float>(),
+                          s_in.data_ptr<float>(), B, F, dim, nd, stride,
+                          de_all.data_ptr<float>(),
+                          want_d_dense ? d_dense->data_ptr<float>() : nullptr,
+                          dw_acc.data_ptr<float>(),
+                          db_acc.data_ptr<float>(), use_fm ? 1 : 0,
+                          out_bf16 ? 1 : 0, S, cur_stream());
+    return {de_all, d_dense};
+}
+
+// (S forward, S backward, blocks of the merged backward, launcher's choice
+// for the backward); S = samples per block, 0 where the shape cannot take
+// the row-staged kernel
+std::tuple<int64_t, int64_t, int64_t, bool> ctr_head_rows_plan(
+    int64_t B, int64_t F, int64_t dim, int64_t nd, int64_t stride,
+    bool out_bf16) {
+    int sf = emb_ctr_head_rows_waves(B, F, dim, nd, stride, out_bf16, 0);
+    int sb = emb_ctr_head_rows_waves(B, F, dim, nd, stride, out_bf16, 1);
+    int sa = emb_ctr_head_rows_waves(B, F, dim, nd, stride, out_bf16, 2);
+    return {sf, sb, sb ? emb_ctr_head_rows_bwd_grid(B, nd, sb) : 0, sa > 0};
 }
 
 // ---- flat dense Adagrad -----------------------------------------------
@@ -1981,8 +2133,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "split owner-reduced payload into grads + int64 counts");
     m.def("ctr_head_fwd", &ctr_head_fwd,
           "fused CTR head fwd: deep_in assembly (+cast) + FM + first-order "
-          "+ dense linear");
-    m.def("ctr_head_bwd", &ctr_head_bwd, "fused CTR head backward");
+          "+ dense linear",
+          pybind11::arg("e_all"), pybind11::arg("dense"), pybind11::arg("w"),
+          pybind11::arg("bias"), pybind11::arg("use_fm"),
+          pybind11::arg("out_bf16"), pybind11::arg("pad32"),
+          pybind11::arg("impl") = 0);
+    m.def("ctr_head_bwd", &ctr_head_bwd, "fused CTR head backward",
+          pybind11::arg("e_all"), pybind11::arg("dense"), pybind11::arg("w"),
+          pybind11::arg("d_deep_in"), pybind11::arg("d_partial"),
+          pybind11::arg("s"), pybind11::arg("use_fm"),
+          pybind11::arg("impl") = 0);
+    m.def("ctr_head_bwd_acc", &ctr_head_bwd_acc,
+          "fused CTR head backward in one launch, dw/db added into the "
+          "caller's buffers",
+          pybind11::arg("e_all"), pybind11::arg("dense"), pybind11::arg("w"),
+          pybind11::arg("d_deep_in"), pybind11::arg("d_partial"),
+          pybind11::arg("s"), pybind11::arg("use_fm"),
+          pybind11::arg("dw_acc"), pybind11::arg("db_acc"),
+          pybind11::arg("want_d_dense") = true);
+    m.def("ctr_head_rows_plan", &ctr_head_rows_plan,
+          "samples per block of the row-staged head kernels for a shape");
     m.def("mlp3_bwd", &mlp3_bwd,
           "fused dgrad chain backward of the 3-layer MLP (optionally "
           "carrying the head wgrad/bias sums)",
