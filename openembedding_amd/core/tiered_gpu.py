@@ -243,6 +243,9 @@ class HipTieredVariableShard(HipVariableShard):
         n = self._nrows_exact
         margin = self._last_batch_upper
         if n + margin <= self.cache_rows:
+            # the conservative bound asked for an eviction the exact count
+            # does not need: this commit evicts nothing and ends the streak
+            self._evict_streak = 0
             return
         # steady thrash (working set >> cache: an eviction every commit):
         # evict deeper so the fixed rebuild cost amortizes over more

@@ -1257,23 +1257,100 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> gather_rows_by_slot(
 #define CHECK_PINNED(t) \
     TORCH_CHECK((t).is_pinned(), #t " must be a pinned host tensor")
 
+// Shared argument checks of the three tier bindings. Every check runs before
+// the launch: a mis-sized call would read or write pinned host memory out of
+// bounds.
+
+// int64 [n] on the GPU, contiguous
+static void tier_check_i64(const torch::Tensor& t, long n, const char* name) {
+    TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+    TORCH_CHECK(t.dtype() == torch::kInt64, name, " must be int64");
+    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+    TORCH_CHECK(n < 0 || t.numel() == n, name, " must hold one entry per key (",
+                n, "), got ", t.numel());
+}
+
+// the device-side host map: tk int64 [cap], tv int32 [cap], cap = 2^k
+static void tier_check_table(const torch::Tensor& htk,
+                             const torch::Tensor& htv) {
+    tier_check_i64(htk, -1, "htk");
+    TORCH_CHECK(htv.is_cuda() && htv.dtype() == torch::kInt32
+                && htv.is_contiguous(), "htv must be a contiguous int32 GPU "
+                "tensor");
+    long cap = htk.numel();
+    TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0,
+                "host table size must be a power of two, got ", cap);
+    TORCH_CHECK(htv.numel() == cap, "htv must be as long as htk (", cap,
+                "), got ", htv.numel());
+}
+
+// float32 [rows, dim] slab on the GPU, contiguous
+static void tier_check_slab(const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+    TORCH_CHECK(t.dtype() == torch::kFloat32 && t.dim() == 2, name,
+                " must be float32 [rows, width]");
+    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+// pinned float32 [rows, width] host slab, contiguous
+static void tier_check_host(const torch::Tensor& t, long width,
+                            const char* name) {
+    TORCH_CHECK(!t.is_cuda() && t.is_pinned(), name,
+                " must be a pinned host tensor");
+    TORCH_CHECK(t.dtype() == torch::kFloat32 && t.dim() == 2, name,
+                " must be float32 [rows, width]");
+    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+    TORCH_CHECK(t.size(1) == width, name, " must be ", width,
+                " wide like the cache slab, got ", t.size(1));
+}
+
+// state [R, sd] beside weights [R, dim] (an empty state means sd == 0) and
+// the host state slab that goes with it; returns sd
+static long tier_check_state(const torch::Tensor& weights,
+                             const torch::Tensor& state,
+                             const OptTensor& host_s) {
+    long sd = state.numel() ? state.size(1) : 0;
+    if (sd) {
+        tier_check_slab(state, "state");
+        TORCH_CHECK(state.size(0) >= weights.size(0),
+                    "state must have a row per weights row");
+        TORCH_CHECK(host_s.has_value(), "state tier needs host_s");
+    }
+    if (sd)
+        tier_check_host(*host_s, sd, "host_s");
+    else if (host_s.has_value())    // never dereferenced: only its width
+        TORCH_CHECK(host_s->dim() == 2 && host_s->size(1) == 0,
+                    "host_s must be 0 wide for a table without state");
+    return sd;
+}
+
 void fault_in(torch::Tensor keys, OptTensor u_dev, torch::Tensor htk,
               torch::Tensor htv, torch::Tensor host_w, OptTensor host_s,
               torch::Tensor weights, torch::Tensor state, torch::Tensor slots,
               torch::Tensor new_mask, torch::Tensor faulted) {
     CHECK_GPU(keys); CHECK_CONT(keys); CHECK_CONT(host_w);
     CHECK_PINNED(host_w);
+    long n = keys.numel();
+    tier_check_i64(keys, n, "keys");
+    if (u_dev.has_value())
+        TORCH_CHECK(u_dev->is_cuda() && u_dev->dtype() == torch::kInt32
+                    && u_dev->numel() == 1, "u_dev must be int32[1] on GPU");
+    tier_check_table(htk, htv);
+    tier_check_slab(weights, "weights");
+    tier_check_host(host_w, weights.size(1), "host_w");
+    long sd = tier_check_state(weights, state, host_s);
+    tier_check_i64(slots, n, "slots");
+    TORCH_CHECK(new_mask.is_cuda() && new_mask.dtype() == torch::kUInt8
+                && new_mask.is_contiguous() && new_mask.numel() == n,
+                "new_mask must be a contiguous uint8 GPU tensor with one "
+                "entry per key (", n, ")");
+    TORCH_CHECK(faulted.is_cuda() && faulted.dtype() == torch::kInt32
+                && faulted.numel() == 1, "faulted must be int32[1] on GPU");
     const c10::cuda::CUDAGuard guard(keys.device());
-    long sd = state.numel() ? state.size(1) : 0;
-    const float* hs = nullptr;
-    if (sd) {
-        TORCH_CHECK(host_s.has_value(), "state tier needs host_s");
-        CHECK_PINNED(*host_s);
-        hs = host_s->data_ptr<float>();
-    }
-    emb_fault_in(keys.data_ptr<i64>(), keys.numel(), u_ptr(u_dev),
+    emb_fault_in(keys.data_ptr<i64>(), n, u_ptr(u_dev),
                  (const u64*)htk.data_ptr<i64>(), htv.data_ptr<int>(),
-                 htk.numel(), host_w.data_ptr<float>(), hs,
+                 htk.numel(), host_w.data_ptr<float>(),
+                 sd ? host_s->data_ptr<float>() : nullptr,
                  weights.data_ptr<float>(),
                  sd ? state.data_ptr<float>() : nullptr, weights.size(1), sd,
                  slots.data_ptr<i64>(), new_mask.data_ptr<uint8_t>(),
@@ -1285,19 +1362,19 @@ void spill_rows(torch::Tensor cache_slots, torch::Tensor host_slots,
                 torch::Tensor host_w, OptTensor host_s) {
     CHECK_GPU(cache_slots); CHECK_CONT(cache_slots); CHECK_CONT(host_slots);
     CHECK_PINNED(host_w);
+    long n = cache_slots.numel();
+    tier_check_i64(cache_slots, n, "cache_slots");
+    tier_check_i64(host_slots, n, "host_slots");
+    tier_check_slab(weights, "weights");
+    tier_check_host(host_w, weights.size(1), "host_w");
+    long sd = tier_check_state(weights, state, host_s);
     const c10::cuda::CUDAGuard guard(cache_slots.device());
-    long sd = state.numel() ? state.size(1) : 0;
-    float* hs = nullptr;
-    if (sd) {
-        TORCH_CHECK(host_s.has_value(), "state tier needs host_s");
-        CHECK_PINNED(*host_s);
-        hs = host_s->data_ptr<float>();
-    }
     emb_spill_rows(cache_slots.data_ptr<i64>(), host_slots.data_ptr<i64>(),
-                   cache_slots.numel(), weights.data_ptr<float>(),
+                   n, weights.data_ptr<float>(),
                    sd ? state.data_ptr<float>() : nullptr,
-                   host_w.data_ptr<float>(), hs, weights.size(1), sd,
-                   cur_stream());
+                   host_w.data_ptr<float>(),
+                   sd ? host_s->data_ptr<float>() : nullptr, weights.size(1),
+                   sd, cur_stream());
 }
 
 void gather_host(torch::Tensor keys, torch::Tensor cache_slots,
@@ -1305,9 +1382,16 @@ void gather_host(torch::Tensor keys, torch::Tensor cache_slots,
                  torch::Tensor out) {
     CHECK_GPU(keys); CHECK_CONT(keys); CHECK_CONT(out);
     CHECK_PINNED(host_w);
+    long n = keys.numel();
+    tier_check_i64(keys, n, "keys");
+    tier_check_i64(cache_slots, n, "cache_slots");
+    tier_check_table(htk, htv);
+    tier_check_slab(out, "out");
+    TORCH_CHECK(out.size(0) == n, "out must have one row per key (", n,
+                "), got ", out.size(0));
+    tier_check_host(host_w, out.size(1), "host_w");
     const c10::cuda::CUDAGuard guard(keys.device());
-    emb_gather_host(keys.data_ptr<i64>(), keys.numel(),
-                    cache_slots.data_ptr<i64>(),
+    emb_gather_host(keys.data_ptr<i64>(), n, cache_slots.data_ptr<i64>(),
                     (const u64*)htk.data_ptr<i64>(), htv.data_ptr<int>(),
                     htk.numel(), host_w.data_ptr<float>(),
                     out.data_ptr<float>(), out.size(1), cur_stream());
