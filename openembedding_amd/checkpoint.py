@@ -28,7 +28,11 @@ section format, only the rows changed since an epoch, and ``apply_delta``
 upserts them on top of a loaded base. The meta of a tracked full dump gains
 ``epoch`` and ``model_uuid``; a delta's meta gains
 ``"delta": {since, epoch, model_uuid}`` and its section headers
-``"delta": true``. Rows are never deleted, so deltas hold upserts only.
+``"delta": true``. Rows removed since that epoch (``expire_rows``, or a
+shard's ``remove_rows``) travel as tombstones: per storage and rank that has
+any, a file ``removed_<rank>`` of sections {header with ``"removed": true``,
+blocks of {n, keys[n]}}. ``apply_delta`` removes first and upserts second,
+so a key that expired and came back inside the interval survives.
 """
 
 from __future__ import annotations
@@ -95,7 +99,8 @@ def _advance(ctx, epoch: int, reset: bool = False) -> None:
 def dump_model(ctx, uri: str, include_optimizer: bool = True) -> None:
     """Collective: every rank writes its shard of every storage. With
     change tracking on, the meta also records the dump's ``epoch`` and the
-    ``model_uuid`` (the base of a delta chain), and the epoch advances."""
+    ``model_uuid`` (the base of a delta chain), the epoch advances and the
+    removal log is pruned."""
     meta = _model_meta(ctx)
     epoch = tracked_epoch(ctx)
     if epoch is not None:
@@ -104,6 +109,9 @@ def dump_model(ctx, uri: str, include_optimizer: bool = True) -> None:
     _write_dump(ctx, uri, meta, include_optimizer, None)
     if epoch is not None:
         _advance(ctx, epoch + 1)
+        # a full dump is a state any consumer can reload: the removals
+        # before it need not be kept for later deltas
+        _prune_removed(ctx, epoch + 1)
 
 
 def dump_delta(ctx, uri: str, include_optimizer: bool = True,
@@ -112,9 +120,13 @@ def dump_delta(ctx, uri: str, include_optimizer: bool = True,
     since the last dump of either kind, which chains the deltas; an explicit
     earlier ``since`` serves a consumer that is further behind). Same layout
     and shard-file format as ``dump_model``, so ``iter_blocks`` reads it;
-    the meta carries ``"delta": {since, epoch, model_uuid}``. Rows are never
-    deleted from a table, so a delta holds upserts only. Returns
-    ``{"since", "epoch", "rows"}`` (rows of this rank)."""
+    the meta carries ``"delta": {since, epoch, model_uuid}``. The keys
+    removed since ``since`` are written as tombstones (``removed_<rank>``
+    files, read by ``iter_removed``); a delta without removals has none. An
+    explicit ``since`` below the epoch at which a full dump or a load pruned
+    logged removals raises ValueError: those removals are gone, so the
+    consumer has to reload the base. Returns ``{"since", "epoch", "rows"}``
+    (rows of this rank)."""
     epoch = tracked_epoch(ctx)
     if epoch is None:
         raise RuntimeError("dump_delta needs change tracking: call "
@@ -123,12 +135,91 @@ def dump_delta(ctx, uri: str, include_optimizer: bool = True,
     since = epoch if since is None else int(since)
     if since < 1 or since > epoch:
         raise ValueError(f"since must be in [1, {epoch}], got {since}")
+    pruned = getattr(ctx, "removals_pruned_epoch", None)
+    if pruned is not None and since < pruned:
+        raise ValueError(
+            f"since={since} reaches below epoch {pruned}, where a full dump "
+            "or a load pruned the log of removed rows: a delta from there "
+            "would miss removals. Reload the base (the latest full dump) "
+            f"and ask for deltas with since >= {pruned}")
     meta = _model_meta(ctx)
     meta["delta"] = {"since": since, "epoch": epoch,
                      "model_uuid": ctx.model_uuid}
     rows = _write_dump(ctx, uri, meta, include_optimizer, since)
+    _write_removed(ctx, uri, since)
     _advance(ctx, epoch + 1)
     return {"since": since, "epoch": epoch, "rows": rows}
+
+
+def expire_rows(ctx, max_age: Optional[int] = None,
+                before: Optional[int] = None) -> dict:
+    """Every rank calls it (no communication): remove, from every variable,
+    the rows last written before epoch ``before`` (default: the current
+    epoch minus ``max_age``; exactly one of the two is given). Needs a
+    tracked context. The removed keys are logged and written as tombstones
+    by the next ``dump_delta``. Returns ``{"before", "rows"}`` (rows removed
+    on this rank)."""
+    if (max_age is None) == (before is None):
+        raise ValueError("give exactly one of max_age and before")
+    epoch = tracked_epoch(ctx)
+    if epoch is None:
+        raise RuntimeError("expire_rows needs change tracking: call "
+                           "track_server_model_changes() (or set "
+                           "server.track_changes) before training")
+    before = epoch - int(max_age) if before is None else int(before)
+    rows = 0
+    for sh in _shards(ctx):
+        rows += int(sh.expire_rows(before).numel())
+    return {"before": before, "rows": rows}
+
+
+def _prune_removed(ctx, epoch: int, reset: bool = False) -> None:
+    """Forget every shard's removal log; if any rank dropped entries,
+    remember ``epoch`` as the lowest ``since`` a delta can still serve.
+    ``reset`` (a load: the epochs start over) forgets an earlier mark."""
+    dropped = False
+    for sh in _shards(ctx):
+        if getattr(sh, "tracking", False):
+            dropped = sh.prune_removed() or dropped
+    if ctx.world_size > 1 and torch.distributed.is_initialized():
+        box = [None] * ctx.world_size
+        torch.distributed.all_gather_object(box, dropped)
+        dropped = any(box)
+    if dropped:
+        ctx.removals_pruned_epoch = int(epoch)
+    elif reset:
+        ctx.removals_pruned_epoch = None
+
+
+def _write_removed(ctx, uri: str, since: int) -> None:
+    """The tombstones of a delta: ``<storage>/removed_<rank>`` with one
+    section per variable that has removals logged at epochs >= since."""
+    for st in ctx.storages:
+        f = None
+        try:
+            for var in st.variables:
+                sh = var.shard
+                if not getattr(sh, "tracking", False):
+                    continue
+                keys = sh.removed_since(since)
+                n = int(keys.numel())
+                if not n:
+                    continue
+                if f is None:
+                    f = open(os.path.join(uri, str(st.storage_id),
+                                          f"removed_{ctx.rank}"), "wb")
+                _write_header(f, {"variable_id": sh.meta.variable_id,
+                                  "num_items": n, "removed": True})
+                keys = keys.cpu().numpy().astype("<i8")
+                for start in range(0, n, BLOCK_ROWS):
+                    blk = keys[start:start + BLOCK_ROWS]
+                    f.write(struct.pack("<q", int(blk.size)))
+                    f.write(blk.tobytes())
+                f.write(struct.pack("<q", -1))
+        finally:
+            if f is not None:
+                f.close()
+    ctx.barrier()
 
 
 def _model_meta(ctx) -> dict:
@@ -310,6 +401,33 @@ def iter_blocks(uri: str, meta: Optional[dict] = None):
                         yield hdr, keys, w, s
 
 
+def iter_removed(uri: str, meta: Optional[dict] = None):
+    """Stream the tombstones of a delta: yields (header_dict, keys <i8 [n])
+    per block of every ``removed_<rank>`` file. Nothing for a directory
+    without removals."""
+    meta = meta or read_meta(uri)
+    for st_ord in range(meta["num_storages"]):
+        d = os.path.join(uri, str(st_ord))
+        for fname in sorted(os.listdir(d)):
+            if not fname.startswith("removed_"):
+                continue
+            with open(os.path.join(d, fname), "rb") as f:
+                while True:
+                    magic = f.read(8)
+                    if not magic:
+                        break
+                    if magic != MAGIC:
+                        raise RuntimeError(f"bad removal file {fname}")
+                    (hlen,) = struct.unpack("<q", f.read(8))
+                    hdr = json.loads(f.read(hlen))
+                    while True:
+                        (blk,) = struct.unpack("<q", f.read(8))
+                        if blk < 0:
+                            break
+                        yield hdr, np.frombuffer(f.read(blk * 8),
+                                                 dtype="<i8")
+
+
 def load_model(ctx, uri: str) -> None:
     """Collective: clears all variables, streams every shard file and keeps
     the keys this rank owns (key % world == rank), re-sharding like the
@@ -318,8 +436,8 @@ def load_model(ctx, uri: str) -> None:
     A delta directory is refused (loading clears the tables; use
     ``apply_delta``). The context remembers the dump's ``epoch`` and
     ``model_uuid`` as the base of a delta chain; a tracking context forgets
-    its stamps and continues at ``epoch + 1`` under the dump's uuid, so the
-    base is not re-emitted by its next delta."""
+    its stamps and its removal log and continues at ``epoch + 1`` under the
+    dump's uuid, so the base is not re-emitted by its next delta."""
     meta = read_meta(uri)
     if "delta" in meta:
         raise RuntimeError(f"{uri} is a delta checkpoint: load its base "
@@ -336,6 +454,7 @@ def load_model(ctx, uri: str) -> None:
             _advance(ctx, ctx.loaded_epoch + 1, reset=True)
         else:
             _advance(ctx, tracked_epoch(ctx), reset=True)
+        _prune_removed(ctx, tracked_epoch(ctx), reset=True)
     ctx.barrier()
 
 
@@ -364,14 +483,18 @@ def check_delta(meta: dict, loaded_uuid, loaded_epoch) -> dict:
 
 
 def apply_delta(ctx, uri: str) -> dict:
-    """Collective: upsert a delta's rows into the loaded tables (nothing is
-    cleared), re-sharded by key % world like ``load_model``. Refused with
+    """Collective: remove the delta's tombstoned keys, then upsert its rows
+    into the loaded tables (nothing is cleared), both re-sharded by
+    key % world like ``load_model``. Removals go first: a key that expired
+    and was re-created inside the interval is in both lists and must
+    survive. Refused with
     RuntimeError, before anything changes, unless ``check_delta`` passes.
     Afterwards ``ctx.loaded_epoch`` is the delta's epoch."""
     meta = read_meta(uri)
     d = check_delta(meta, getattr(ctx, "loaded_model_uuid", None),
                     getattr(ctx, "loaded_epoch", None))
     by_id = _match_variables(ctx, meta)
+    _remove_blocks(ctx, uri, meta, by_id)
     _import_blocks(ctx, uri, meta, by_id)
     ctx.loaded_epoch = d["epoch"]
     epoch = tracked_epoch(ctx)
@@ -395,6 +518,22 @@ def _match_variables(ctx, meta: dict) -> dict:
             raise RuntimeError(f"variable {vid}: dim mismatch "
                                f"{v.shard.dim} != {mvar['embedding_dim']}")
     return by_id
+
+
+def _remove_blocks(ctx, uri: str, meta: dict, by_id: dict) -> int:
+    """Apply a delta's tombstones to this rank's shards; returns how many
+    rows went."""
+    rank, world = ctx.rank, ctx.world_size
+    gone = 0
+    for hdr, keys in iter_removed(uri, meta):
+        var = by_id.get(hdr["variable_id"])
+        if var is None:
+            continue
+        mine = keys[(keys % world) == rank]
+        if mine.size:
+            kt = torch.from_numpy(mine.copy()).to(ctx.device)
+            gone += int(var.shard.remove_rows(kt).numel())
+    return gone
 
 
 def _import_blocks(ctx, uri: str, meta: dict, by_id: dict) -> None:

@@ -1,7 +1,8 @@
 """Quantized serving table: one read-only shard stored as packed rows.
 
-A serving replica never writes its tables again after the load, so it needs
-neither fp32 rows nor an optimizer-state slab nor a grow-by-doubling policy.
+A serving replica only receives rows (a load, a delta's upserts and
+tombstones) and never trains them, so it needs neither fp32 rows nor an
+optimizer-state slab nor a grow-by-doubling policy.
 ``QuantizedShard`` owns exactly two things: a key -> row map (the hash
 ``tk`` / ``tv`` / ``slot_keys`` or the array ``valid_u8`` of the training
 shards, built with the same kernels) and a ``torch.uint8`` slab
@@ -27,7 +28,7 @@ import torch
 
 from ..ops import dispatch as ops
 from ..ops import require_hip
-from .variable import VariableMeta
+from .variable import VariableMeta, hole_fill_plan
 
 
 class QuantizedShard:
@@ -344,6 +345,63 @@ class QuantizedShard:
             keys = slots * self.shard_num + self.shard_id
             packed = self.slab[slots]
         return keys, ops.dequantize_rows(packed, self.dim, self.fmt), None
+
+    # -------------------------------------------------------------- removal
+
+    def remove_rows(self, keys: torch.Tensor) -> torch.Tensor:
+        """Remove the rows of ``keys`` (a delta's tombstones; unknown keys,
+        duplicates and the reserved key -1 are ignored), with the layout
+        rule of ``VariableShard.remove_rows``: a hash table moves its last
+        rows into the holes, an array table clears the valid byte. On a GPU
+        the expiry kernels of the training shards run over ``slab`` /
+        ``slot_keys`` / ``tk`` / ``tv`` / ``nrows_dev`` in place; the CPU
+        form is their oracle (equal slab bytes). Returns the removed keys,
+        int64 on the shard's device, in ascending old-slot order."""
+        keys = keys.to(self.device, torch.int64).reshape(-1).contiguous()
+        if self.meta.use_hash_table:
+            return self._remove_hashed(keys)
+        # array table: keys of another shard or outside the vocabulary miss
+        ok = ((keys >= 0) & (keys % self.shard_num == self.shard_id)
+              & (keys // self.shard_num < self._array_cap))
+        slots = torch.where(ok, keys // self.shard_num,
+                            torch.full_like(keys, -1))
+        if self._hip:
+            dead = self.ext.flag_slots(slots, self._array_cap)
+            gone = self.ext.remove_flagged_array(dead, self.valid_u8,
+                                                 self.shard_num,
+                                                 self.shard_id)
+        else:
+            slots = torch.unique(slots[ok])
+            slots = slots[self.valid_u8[slots] != 0]
+            self.valid_u8[slots] = 0
+            gone = slots * self.shard_num + self.shard_id
+        self._nrows -= int(gone.numel())
+        return gone
+
+    def _remove_hashed(self, keys: torch.Tensor) -> torch.Tensor:
+        if self._hip:
+            slots, _ = self.ext.ht_lookup(self.tk, self.tv, keys,
+                                          self.nrows_dev, self.slot_keys,
+                                          False, None)
+            dead = self.ext.flag_slots(slots, self.slot_keys.numel())
+            gone, n2 = self.ext.remove_flagged(
+                dead, [self.slab, self.slot_keys], self.slot_keys, self.tk,
+                self.tv, self.nrows_dev)
+            self._nrows = int(n2)
+            return gone
+        idx = self._index
+        dead = torch.zeros(self._nrows, dtype=torch.bool, device=self.device)
+        dead[[idx[k] for k in keys.tolist() if k in idx]] = True
+        dead_slots, holes, movers = hole_fill_plan(dead, self._nrows)
+        gone = self.slot_keys[dead_slots]
+        for k in gone.tolist():
+            del idx[k]
+        for k, h in zip(self.slot_keys[movers].tolist(), holes.tolist()):
+            idx[k] = h
+        self.slab[holes] = self.slab[movers]
+        self.slot_keys[holes] = self.slot_keys[movers]
+        self._nrows -= int(dead_slots.numel())
+        return gone
 
     # ---------------------------------------------------------------- writes
 

@@ -368,3 +368,15 @@ class HipTieredVariableShard(HipVariableShard):
                 "change tracking is per cache slot and the capacity tier "
                 "moves rows between slots on eviction: delta checkpoints "
                 "need an untiered variable (server.cache_size_mb = 0)")
+
+    def expire_rows(self, before: int):
+        raise NotImplementedError(
+            "row expiry rewrites the slab in place and the capacity tier "
+            "keeps rows in two tiers: expiry needs an untiered variable "
+            "(server.cache_size_mb = 0)")
+
+    def remove_rows(self, keys):
+        raise NotImplementedError(
+            "row removal rewrites the slab in place and the capacity tier "
+            "keeps rows in two tiers: removal needs an untiered variable "
+            "(server.cache_size_mb = 0)")

@@ -56,6 +56,20 @@ class VariableMeta:
         return {torch.float32: "float32", torch.float64: "float64"}[self.dtype]
 
 
+def hole_fill_plan(dead: torch.Tensor, n: int):
+    """The layout rule of a removal from a slab that is dense in [0, n):
+    ``dead`` (bool, one per slot) flags the m rows that go. Returns
+    (dead_slots, holes, movers), ascending: the holes are the dead slots
+    below n' = n - m, the movers the surviving slots in [n', n); there are
+    equally many, and the i-th mover's row goes to the i-th hole."""
+    dead = dead[:n]
+    dead_slots = dead.nonzero(as_tuple=True)[0]
+    n2 = n - int(dead_slots.numel())
+    holes = dead_slots[dead_slots < n2]
+    surv = (~dead).nonzero(as_tuple=True)[0]
+    return dead_slots, holes, surv[surv >= n2]
+
+
 class VariableShard:
     """One rank's shard of one embedding variable (torch backend)."""
 
@@ -347,21 +361,140 @@ class VariableShard:
             if self._tracking:
                 self.row_epoch.zero_()
 
+    # ------------------------------------------------------------- row expiry
+    # Removal of rows in place. ``expire_rows`` drops the rows last written
+    # before an epoch, ``remove_rows`` the rows of named keys (a delta's
+    # tombstones). A hash table fills its holes: with n live rows of which m
+    # are dead and n' = n - m, the holes are the dead slots < n' and the
+    # movers the surviving slots in [n', n), both ascending; the i-th mover's
+    # row (weights, state, key, stamp) moves to the i-th hole, every other
+    # survivor keeps its slot and the live count becomes n'. Slots >= n' are
+    # dead storage that nothing zeroes. An array table clears the valid bit;
+    # nothing moves. A removed key misses afterwards, and a later training
+    # pull re-creates it through the ordinary lazy init, which is
+    # deterministic in (seed, key). This torch form is the CPU path and the
+    # oracle of the HIP kernels.
+
+    def expire_rows(self, before: int) -> torch.Tensor:
+        """Remove every live row with ``row_epoch < before`` (tracking only;
+        in training every pulled row is written at commit, so the stamp is
+        also "last seen"). Stamps zeroed by ``set_epoch(reset=True)`` are
+        the oldest: after a base was loaded, every row it brought expires
+        under any ``before >= 1`` until it is written again. Returns the
+        removed keys, int64 on the shard's device, in ascending old-slot
+        order, and logs them for the next delta."""
+        self._need_tracking()
+        self._check_removable()
+        return self._log_removed(self._remove_flagged(
+            self._flags_expired(int(before))))
+
+    def remove_rows(self, keys: torch.Tensor) -> torch.Tensor:
+        """Remove the rows of ``keys`` (int64; unknown keys, duplicates and
+        the reserved key -1 are ignored). Works without tracking. Returns
+        the removed keys like ``expire_rows``."""
+        self._check_removable()
+        keys = keys.to(self.device, torch.int64).reshape(-1).contiguous()
+        return self._log_removed(self._remove_flagged(
+            self._flags_named(keys)))
+
+    def _check_removable(self) -> None:
+        if self._pending or getattr(self, "_pending_bounded", None):
+            raise RuntimeError(
+                "rows cannot be removed while gradient blocks are queued "
+                "(their saved slots would go stale): call update_weights() "
+                "first")
+
+    def _owned_slots_readonly(self, keys: torch.Tensor) -> torch.Tensor:
+        """``_lookup_readonly`` that also misses, in array mode, on keys
+        this shard does not own or that lie outside the vocabulary."""
+        if self.meta.use_hash_table:
+            return self._lookup_readonly(keys)
+        ok = ((keys >= 0) & (keys % self.shard_num == self.shard_id)
+              & (keys // self.shard_num < self._array_cap))
+        slots = self._lookup_readonly(torch.where(
+            ok, keys, torch.full_like(keys, self.shard_id)))
+        return torch.where(ok, slots, torch.full_like(slots, -1))
+
+    def _live_mask(self) -> torch.Tensor:
+        if not self.meta.use_hash_table:
+            return self.valid.clone()
+        live = torch.zeros(self.weights.shape[0], dtype=torch.bool,
+                           device=self.device)
+        live[:self._nrows] = True
+        return live
+
+    def _flags_expired(self, before: int) -> torch.Tensor:
+        return self._live_mask() & (self.row_epoch < before)
+
+    def _flags_named(self, keys: torch.Tensor) -> torch.Tensor:
+        dead = torch.zeros(self.weights.shape[0], dtype=torch.bool,
+                           device=self.device)
+        slots = self._owned_slots_readonly(keys)
+        dead[slots[slots >= 0]] = True
+        return dead
+
+    def _remove_flagged(self, dead: torch.Tensor) -> torch.Tensor:
+        """Remove the live rows flagged in ``dead`` (bool, one per slot)."""
+        if not self.meta.use_hash_table:
+            dead_slots = dead.nonzero(as_tuple=True)[0]
+            self.valid[dead_slots] = False
+            return dead_slots * self.shard_num + self.shard_id
+        dead_slots, holes, movers = hole_fill_plan(dead, self._nrows)
+        if dead_slots.numel() == 0:
+            return dead_slots
+        sk = self._slot_key_list()
+        removed = sk[dead_slots]
+        planes = [self.weights, self.state]
+        if self._tracking:
+            planes.append(self.row_epoch)
+        for p in planes:
+            p[holes] = p[movers]
+        idx = self._index
+        for k in removed.tolist():
+            del idx[k]
+        for k, h in zip(sk[movers].tolist(), holes.tolist()):
+            idx[k] = h
+        self._nrows -= int(dead_slots.numel())
+        return removed
+
+    # removal log: (epoch, removed keys) entries, kept while tracking is on
+    # and written by checkpoint.dump_delta as the delta's tombstones
+
+    def _log_removed(self, keys: torch.Tensor) -> torch.Tensor:
+        if self._tracking and keys.numel():
+            self.__dict__.setdefault("_removed_log", []).append(
+                (self._epoch, keys))
+        return keys
+
+    def removed_since(self, since: int) -> torch.Tensor:
+        """The logged removed keys of the epochs ``>= since`` (int64; a key
+        removed twice occurs twice)."""
+        ks = [k for e, k in self.__dict__.get("_removed_log", ())
+              if e >= int(since)]
+        if not ks:
+            return torch.empty(0, dtype=torch.int64, device=self.device)
+        return torch.cat(ks)
+
+    def prune_removed(self) -> bool:
+        """Forget the removal log; True if that dropped any entry."""
+        return bool(self.__dict__.pop("_removed_log", None))
+
     # -------------------------------------------------------- change tracking
     # Delta checkpoints (checkpoint.dump_delta): ``row_epoch[slot]`` is the
     # epoch of the row's last write and ``epoch`` the current one. A row is
     # stamped when a lookup-or-insert creates it, when update_weights applies
     # the optimizer to it, when import_rows writes it and when set_optimizer
-    # rebuilds the state block; reads stamp nothing. Rows are never deleted,
-    # so the rows with ``row_epoch >= since`` are the whole difference. This
-    # torch form is the CPU path and the oracle of the HIP kernels.
+    # rebuilds the state block; reads stamp nothing. A delta is the rows with
+    # ``row_epoch >= since`` plus the keys removed since then (the removal
+    # log above). This torch form is the CPU path and the oracle of the HIP
+    # kernels.
 
     def track_changes(self, enable: bool = True) -> None:
         """Turn change tracking on (row_epoch zeroed, epoch 1) or off (the
         tensors are dropped). Turning it on twice keeps the stamps."""
         if not enable:
             self._tracking = False
-            for name in ("row_epoch", "epoch_dev", "_epoch"):
+            for name in ("row_epoch", "epoch_dev", "_epoch", "_removed_log"):
                 if name in self.__dict__:
                     delattr(self, name)
             return

@@ -505,6 +505,47 @@ class HipVariableShard(VariableShard):
         if self._tracking:
             self.row_epoch.zero_()
 
+    # ------------------------------------------------------------ row expiry
+    # The base class's contract in place on the device (ops/csrc/embops.hip,
+    # "row expiry"): no buffer is reallocated, so a hipGraph captured on a
+    # reserve_rows shard before a removal replays after it (it looks slots up
+    # on every replay and reads nrows_dev through its pointer). The extra
+    # memory is a byte of flags per row and the hole / mover lists. The
+    # removed count is the one host read.
+
+    def _check_removable(self) -> None:
+        super()._check_removable()
+        if self._in_graph_capture():
+            raise RuntimeError("rows cannot be removed under stream capture "
+                               "(the removed count is read on the host)")
+
+    def _flags_expired(self, before: int) -> torch.Tensor:
+        if self.meta.use_hash_table:
+            return self.ext.expire_flags(self.row_epoch, before,
+                                         nrows_dev=self.nrows_dev)
+        return self.ext.expire_flags(self.row_epoch, before,
+                                     valid=self.valid_u8)
+
+    def _flags_named(self, keys: torch.Tensor) -> torch.Tensor:
+        rows = self.slot_keys.numel() if self.meta.use_hash_table \
+            else self._array_cap
+        return self.ext.flag_slots(self._owned_slots_readonly(keys), rows)
+
+    def _remove_flagged(self, dead: torch.Tensor) -> torch.Tensor:
+        if not self.meta.use_hash_table:
+            return self.ext.remove_flagged_array(dead, self.valid_u8,
+                                                 self.shard_num,
+                                                 self.shard_id)
+        planes = [self.weights, self.slot_keys]
+        if self.state_dim:
+            planes.append(self.state)
+        if self._tracking:
+            planes.append(self.row_epoch)
+        keys, n2 = self.ext.remove_flagged(dead, planes, self.slot_keys,
+                                           self.tk, self.tv, self.nrows_dev)
+        self._nrows_exact = self._nrows_upper = int(n2)
+        return keys
+
     # ------------------------------------------------------ change tracking
     # The base class's contract on the device. The epoch lives in
     # ``epoch_dev`` and the stamping kernel reads it through the pointer, so

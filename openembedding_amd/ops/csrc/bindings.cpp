@@ -137,6 +137,22 @@ void emb_delta_compact(const int*, long, int, const int*,
 void emb_delta_gather(const float*, const float*, long, long, long,
                       const i64*, long, long, const i64*, long, long, long,
                       const int*, i64*, float*, float*, hipStream_t_);
+void emb_expire_flag(const int*, long, int, const int*, const unsigned char*,
+                     unsigned char*, hipStream_t_);
+void emb_flag_slots(const i64*, long, unsigned char*, long, hipStream_t_);
+void emb_expire_count(int, const unsigned char*, long, const int*,
+                      const unsigned char*, const int*, int*, hipStream_t_);
+void emb_expire_counts(const int*, long, const int*, long, int*,
+                       hipStream_t_);
+void emb_expire_compact(int, const unsigned char*, long, const int*,
+                        const unsigned char*, const int*, const int*, int*,
+                        i64*, const i64*, long, long, long, hipStream_t_);
+void emb_move_rows(void*, long, long, const int*, const int*, long,
+                   const int*, hipStream_t_);
+void emb_ht_build(u64*, int*, long, const i64*, long, const int*, int*, long,
+                  hipStream_t_);
+void emb_expire_array(unsigned char*, const unsigned char*, long,
+                      hipStream_t_);
 void emb_fault_in(const i64*, long, const int*, const u64*, const int*, long,
                   const float*, const float*, float*, float*, long, long,
                   const i64*, unsigned char*, int*, hipStream_t_);
@@ -1249,6 +1265,175 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> gather_rows_by_slot(
     return {ko, wo, so};
 }
 
+// ---- row expiry -----------------------------------------------------------
+// Removal of rows in place. The caller flags the dead rows (expire_flags by
+// age, flag_slots by name); remove_flagged / remove_flagged_array do the rest
+// and return the removed keys in ascending old-slot order.
+
+static void check_dead(const torch::Tensor& dead) {
+    CHECK_GPU(dead); CHECK_CONT(dead);
+    TORCH_CHECK(dead.dtype() == torch::kUInt8 && dead.dim() == 1,
+                "dead must be uint8 [R]");
+}
+
+static const int* nrows_ptr(const torch::Tensor& nrows_dev) {
+    CHECK_GPU(nrows_dev);
+    TORCH_CHECK(nrows_dev.dtype() == torch::kInt32 && nrows_dev.numel() == 1,
+                "nrows_dev must be int32[1]");
+    return nrows_dev.data_ptr<int>();
+}
+
+// dead uint8 [R]: the live rows with row_epoch < before
+torch::Tensor expire_flags(torch::Tensor row_epoch, int64_t before,
+                           OptTensor nrows_dev, OptTensor valid) {
+    CHECK_GPU(row_epoch); CHECK_CONT(row_epoch);
+    TORCH_CHECK(row_epoch.dtype() == torch::kInt32,
+                "row_epoch must be int32");
+    TORCH_CHECK(nrows_dev.has_value() != valid.has_value(),
+                "expire_flags takes nrows_dev (hash) or valid (array)");
+    TORCH_CHECK(before >= INT32_MIN && before <= INT32_MAX, "before range");
+    long R = row_epoch.numel();
+    const int* np = nullptr;
+    const unsigned char* vp = nullptr;
+    if (nrows_dev.has_value()) {
+        np = nrows_ptr(*nrows_dev);
+    } else {
+        CHECK_GPU(*valid); CHECK_CONT(*valid);
+        TORCH_CHECK(valid->element_size() == 1 && valid->numel() == R,
+                    "valid must hold one byte per row");
+        vp = static_cast<const unsigned char*>(valid->data_ptr());
+    }
+    const c10::cuda::CUDAGuard guard(row_epoch.device());
+    auto dead = torch::empty({R}, row_epoch.options().dtype(torch::kUInt8));
+    emb_expire_flag(row_epoch.data_ptr<int>(), R, (int)before, np, vp,
+                    dead.data_ptr<uint8_t>(), cur_stream());
+    return dead;
+}
+
+// dead uint8 [rows]: 1 at the named slots (misses and duplicates allowed)
+torch::Tensor flag_slots(torch::Tensor slots, int64_t rows) {
+    CHECK_GPU(slots); CHECK_CONT(slots);
+    TORCH_CHECK(slots.dtype() == torch::kInt64, "slots must be int64");
+    TORCH_CHECK(rows >= 0, "rows must be >= 0");
+    const c10::cuda::CUDAGuard guard(slots.device());
+    auto dead = torch::empty({rows}, slots.options().dtype(torch::kUInt8));
+    emb_flag_slots(slots.data_ptr<i64>(), slots.numel(),
+                   dead.data_ptr<uint8_t>(), rows, cur_stream());
+    return dead;
+}
+
+// count + scan of one compaction: the inclusive tile sums [T]
+static torch::Tensor expire_scan(int mode, const torch::Tensor& dead,
+                                 const int* np, const unsigned char* vp,
+                                 const int* cnt) {
+    long R = dead.numel();
+    auto i32 = dead.options().dtype(torch::kInt32);
+    auto counts = torch::empty({emb_delta_tiles(R)}, i32);
+    emb_expire_count(mode, dead.data_ptr<uint8_t>(), R, np, vp, cnt,
+                     counts.data_ptr<int>(), cur_stream());
+    return torch::cumsum(counts, 0, torch::kInt32);
+}
+
+// Hash table: remove the flagged live rows in place. planes are the
+// per-row buffers ([rows, ...] contiguous, a whole number of 32-bit words
+// per row; slot_keys must be one of them); every one keeps its storage.
+// Returns (removed keys int64 [m], n'). The one host read is of {m, n'}.
+std::tuple<torch::Tensor, int64_t> remove_flagged(
+    torch::Tensor dead, std::vector<torch::Tensor> planes,
+    torch::Tensor slot_keys, torch::Tensor tk, torch::Tensor tv,
+    torch::Tensor nrows_dev) {
+    check_dead(dead);
+    long R = dead.numel();
+    CHECK_GPU(slot_keys); CHECK_CONT(slot_keys);
+    TORCH_CHECK(slot_keys.dtype() == torch::kInt64 && slot_keys.numel() >= R,
+                "slot_keys must be int64 with a key per flagged row");
+    CHECK_GPU(tk); CHECK_CONT(tk); CHECK_GPU(tv); CHECK_CONT(tv);
+    long cap = tk.numel();
+    TORCH_CHECK(tk.dtype() == torch::kInt64 && tv.dtype() == torch::kInt32
+                && tv.numel() == cap && cap > 0 && (cap & (cap - 1)) == 0,
+                "tk/tv must be an int64/int32 table of power-of-two size");
+    const int* np = nrows_ptr(nrows_dev);
+    std::vector<long> wpr;
+    bool has_keys = false;
+    for (const auto& p : planes) {
+        CHECK_GPU(p); CHECK_CONT(p);
+        TORCH_CHECK(p.dim() >= 1 && p.size(0) >= R,
+                    "a plane must hold a row per flagged row");
+        long row_bytes = p.size(0) ? (long)(p.numel() / p.size(0))
+                                         * (long)p.element_size() : 0;
+        TORCH_CHECK(row_bytes % 4 == 0,
+                    "a plane's rows must be whole 32-bit words");
+        wpr.push_back(row_bytes / 4);
+        has_keys = has_keys || p.data_ptr() == slot_keys.data_ptr();
+    }
+    TORCH_CHECK(has_keys, "slot_keys must be among the planes");
+    const c10::cuda::CUDAGuard guard(dead.device());
+    auto i32 = dead.options().dtype(torch::kInt32);
+    auto i64o = dead.options().dtype(torch::kInt64);
+    if (R == 0) return {torch::empty({0}, i64o), 0};
+    long T = emb_delta_tiles(R);
+    const uint8_t* dp = dead.data_ptr<uint8_t>();
+    auto cnt = torch::empty({2}, i32);
+    auto incl_d = expire_scan(0, dead, np, nullptr, nullptr);
+    emb_expire_counts(incl_d.data_ptr<int>(), T, np, R, cnt.data_ptr<int>(),
+                      cur_stream());
+    auto host = cnt.cpu();   // the one host read: {m, n'}
+    long m = host.data_ptr<int>()[0], nprime = host.data_ptr<int>()[1];
+    auto keys = torch::empty({m}, i64o);
+    if (m == 0) return {keys, nprime};
+    // the removed keys, before any row moves
+    emb_expire_compact(0, dp, R, np, nullptr, nullptr,
+                       incl_d.data_ptr<int>(), nullptr, keys.data_ptr<i64>(),
+                       slot_keys.data_ptr<i64>(), 1, 0, m, cur_stream());
+    long h = m < nprime ? m : nprime;   // bound of the hole count
+    if (h > 0) {
+        auto holes = torch::empty({h}, i32);
+        auto movers = torch::empty({h}, i32);
+        auto incl_h = expire_scan(1, dead, np, nullptr, cnt.data_ptr<int>());
+        emb_expire_compact(1, dp, R, np, nullptr, cnt.data_ptr<int>(),
+                           incl_h.data_ptr<int>(), holes.data_ptr<int>(),
+                           nullptr, nullptr, 1, 0, h, cur_stream());
+        auto incl_m = expire_scan(2, dead, np, nullptr, cnt.data_ptr<int>());
+        emb_expire_compact(2, dp, R, np, nullptr, cnt.data_ptr<int>(),
+                           incl_m.data_ptr<int>(), movers.data_ptr<int>(),
+                           nullptr, nullptr, 1, 0, h, cur_stream());
+        const int* moves = incl_h.data_ptr<int>() + (T - 1);
+        for (size_t i = 0; i < planes.size(); ++i)
+            emb_move_rows(planes[i].data_ptr(), R, wpr[i],
+                          holes.data_ptr<int>(), movers.data_ptr<int>(), h,
+                          moves, cur_stream());
+    }
+    emb_ht_build((u64*)tk.data_ptr<i64>(), tv.data_ptr<int>(), cap,
+                 slot_keys.data_ptr<i64>(), R, cnt.data_ptr<int>(),
+                 nrows_dev.data_ptr<int>(), nprime, cur_stream());
+    return {keys, nprime};
+}
+
+// Array table: clear the valid byte of the flagged live rows; returns their
+// keys (slot * shard_num + shard_id, ascending). One host read (the count).
+torch::Tensor remove_flagged_array(torch::Tensor dead, torch::Tensor valid,
+                                   int64_t shard_num, int64_t shard_id) {
+    check_dead(dead);
+    long R = dead.numel();
+    CHECK_GPU(valid); CHECK_CONT(valid);
+    TORCH_CHECK(valid.element_size() == 1 && valid.numel() == R,
+                "valid must hold one byte per row");
+    const c10::cuda::CUDAGuard guard(dead.device());
+    auto i64o = dead.options().dtype(torch::kInt64);
+    if (R == 0) return torch::empty({0}, i64o);
+    long T = emb_delta_tiles(R);
+    auto vp = static_cast<unsigned char*>(valid.data_ptr());
+    auto incl = expire_scan(0, dead, nullptr, vp, nullptr);
+    long m = incl.slice(0, T - 1, T).item<int>();   // the one host read
+    auto keys = torch::empty({m}, i64o);
+    if (m == 0) return keys;
+    emb_expire_compact(0, dead.data_ptr<uint8_t>(), R, nullptr, vp, nullptr,
+                       incl.data_ptr<int>(), nullptr, keys.data_ptr<i64>(),
+                       nullptr, shard_num, shard_id, m, cur_stream());
+    emb_expire_array(vp, dead.data_ptr<uint8_t>(), R, cur_stream());
+    return keys;
+}
+
 // ---- capacity tier v2 --------------------------------------------------
 // Pinned host tensors are device-accessible on ROCm (hipHostMalloc-backed
 // via the torch pinned allocator): the fault-in/spill kernels read/write
@@ -2199,6 +2384,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("keys_out") = pybind11::none(),
           pybind11::arg("w_out") = pybind11::none(),
           pybind11::arg("s_out") = pybind11::none());
+    m.def("expire_flags", &expire_flags,
+          "row expiry: dead uint8 [R] = live rows with row_epoch < before",
+          pybind11::arg("row_epoch"), pybind11::arg("before"),
+          pybind11::arg("nrows_dev") = pybind11::none(),
+          pybind11::arg("valid") = pybind11::none());
+    m.def("flag_slots", &flag_slots,
+          "row expiry: dead uint8 [rows] = 1 at the named slots",
+          pybind11::arg("slots"), pybind11::arg("rows"));
+    m.def("remove_flagged", &remove_flagged,
+          "row expiry (hash table): fill the holes of the flagged rows in "
+          "place over every plane and rebuild the probe table -> (removed "
+          "keys in old-slot order, live rows left)",
+          pybind11::arg("dead"), pybind11::arg("planes"),
+          pybind11::arg("slot_keys"), pybind11::arg("tk"),
+          pybind11::arg("tv"), pybind11::arg("nrows_dev"));
+    m.def("remove_flagged_array", &remove_flagged_array,
+          "row expiry (array table): clear the valid byte of the flagged "
+          "rows -> removed keys, ascending",
+          pybind11::arg("dead"), pybind11::arg("valid"),
+          pybind11::arg("shard_num") = 1, pybind11::arg("shard_id") = 0);
     m.def("fault_in", &fault_in,
           "tier v2: copy host-resident rows into fresh cache slots, "
           "clearing their lazy-init mask");

@@ -2699,6 +2699,199 @@ __global__ void k_delta_gather(const float* __restrict__ weights,
     }
 }
 
+// ------------------------------------------------------------- row expiry
+// Removal of rows in place (maintenance, between steps). The caller flags
+// the dead rows in dead[R]; the ordered compaction above, over other
+// predicates, lists the removed keys, the holes and the movers, a move kernel
+// fills the holes plane by plane and the probe table is rebuilt from
+// slot_keys. With n live rows of which m are dead and n' = n - m:
+//   XP_DEAD   live rows that are flagged            (their keys are returned)
+//   XP_HOLE   flagged rows below n'                 (destinations)
+//   XP_MOVER  live rows at or above n' not flagged  (sources)
+// There are as many holes as movers, and the i-th mover goes to the i-th
+// hole. cnt = {m, n'} lives on the device: XP_HOLE / XP_MOVER read n' there.
+// An array table (valid != null) has XP_DEAD only: nothing moves.
+#define XP_DEAD 0
+#define XP_HOLE 1
+#define XP_MOVER 2
+
+// dead[r] = row r is live and was last written before epoch `before`
+__global__ void k_expire_flag(const int* __restrict__ row_epoch, long R,
+                              int before, const int* __restrict__ nrows_dev,
+                              const unsigned char* __restrict__ valid,
+                              unsigned char* __restrict__ dead) {
+    long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    bool live = valid ? valid[r] != 0 : r < delta_live(nrows_dev, R);
+    dead[r] = (live && row_epoch[r] < before) ? 1 : 0;
+}
+
+// dead[slot] = 1 for the named rows; misses (-1) and slots outside the slab
+// are skipped, duplicates store the same value (benign)
+__global__ void k_flag_slots(const i64* __restrict__ slots, long n,
+                             unsigned char* __restrict__ dead, long R) {
+    long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    i64 s = slots[g];
+    if (s < 0 || s >= R) return;
+    dead[s] = 1;
+}
+
+template <int MODE>
+DEV bool expire_pred(const unsigned char* __restrict__ dead, long r, long R,
+                     long live, long np,
+                     const unsigned char* __restrict__ valid) {
+    if (r >= R) return false;
+    if (valid) return MODE == XP_DEAD && valid[r] != 0 && dead[r] != 0;
+    if (r >= live) return false;
+    if (MODE == XP_DEAD) return dead[r] != 0;
+    if (MODE == XP_HOLE) return r < np && dead[r] != 0;
+    return r >= np && dead[r] == 0;
+}
+
+// k_delta_count over expire_pred
+template <int MODE>
+__global__ __launch_bounds__(BLOCK)
+void k_expire_count(const unsigned char* __restrict__ dead, long R,
+                    const int* __restrict__ nrows_dev,
+                    const unsigned char* __restrict__ valid,
+                    const int* __restrict__ cnt,
+                    int* __restrict__ tile_counts) {
+    __shared__ int wave_cnt[DT_WAVES];
+    long live = delta_live(nrows_dev, R);
+    long np = MODE == XP_DEAD ? 0 : (long)cnt[1];
+    long base = (long)blockIdx.x * DT_TILE + threadIdx.x;
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < DT_ITEMS; ++i) {
+        bool p = expire_pred<MODE>(dead, base + (long)i * BLOCK, R, live, np,
+                                   valid);
+        c += __popcll(__ballot(p));
+    }
+    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+#pragma unroll
+        for (int w = 0; w < DT_WAVES; ++w) t += wave_cnt[w];
+        tile_counts[blockIdx.x] = t;
+    }
+}
+
+// cnt = {m, n'} from the scanned XP_DEAD tile counts
+__global__ void k_expire_counts(const int* __restrict__ tile_incl, long T,
+                                const int* __restrict__ nrows_dev, long R,
+                                int* __restrict__ cnt) {
+    if (blockIdx.x || threadIdx.x) return;
+    long m = (long)tile_incl[T - 1];
+    cnt[0] = (int)m;
+    cnt[1] = (int)(delta_live(nrows_dev, R) - m);
+}
+
+// k_delta_compact over expire_pred: position pos of the ordered list gets
+// the row (list) and/or its key (keys_out: slot_keys[r], or the array
+// layout's r * shard_num + shard_id); out_cap bounds both
+template <int MODE>
+__global__ __launch_bounds__(BLOCK)
+void k_expire_compact(const unsigned char* __restrict__ dead, long R,
+                      const int* __restrict__ nrows_dev,
+                      const unsigned char* __restrict__ valid,
+                      const int* __restrict__ cnt,
+                      const int* __restrict__ tile_incl,
+                      int* __restrict__ list, i64* __restrict__ keys_out,
+                      const i64* __restrict__ slot_keys, long shard_num,
+                      long shard_id, long out_cap) {
+    __shared__ int wcnt[DT_ITEMS * DT_WAVES];
+    __shared__ int off[DT_ITEMS * DT_WAVES];
+    long live = delta_live(nrows_dev, R);
+    long np = MODE == XP_DEAD ? 0 : (long)cnt[1];
+    long base = (long)blockIdx.x * DT_TILE + threadIdx.x;
+    int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    bool p[DT_ITEMS];
+    int rank[DT_ITEMS];
+#pragma unroll
+    for (int i = 0; i < DT_ITEMS; ++i) {
+        p[i] = expire_pred<MODE>(dead, base + (long)i * BLOCK, R, live, np,
+                                 valid);
+        u64 b = __ballot(p[i]);
+        rank[i] = __popcll(b & below);
+        if (lane == 0) wcnt[i * DT_WAVES + wave] = __popcll(b);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int j = 0; j < DT_ITEMS * DT_WAVES; ++j) {
+            off[j] = run;
+            run += wcnt[j];
+        }
+    }
+    __syncthreads();
+    long tile_base = blockIdx.x ? (long)tile_incl[blockIdx.x - 1] : 0;
+#pragma unroll
+    for (int i = 0; i < DT_ITEMS; ++i) {
+        if (!p[i]) continue;
+        long r = base + (long)i * BLOCK;
+        long pos = tile_base + off[i * DT_WAVES + wave] + rank[i];
+        if (pos < 0 || pos >= out_cap) continue;
+        if (list) list[pos] = (int)r;
+        if (keys_out)
+            keys_out[pos] = slot_keys ? slot_keys[r]
+                                      : r * shard_num + shard_id;
+    }
+}
+
+// Row move over one plane of 32-bit words: row movers[i] -> row holes[i] for
+// i < *count_dev, one G-lane group per row, coalesced along the row. Every
+// source lies in [n', n) and every destination in [0, n'): the two ranges
+// are disjoint, no row is both read and written, so the parallel in-place
+// move is race free in any order (the dst < src test below enforces it).
+template <int G>
+__global__ void k_move_rows(unsigned* __restrict__ base, long R, long wpr,
+                            const int* __restrict__ holes,
+                            const int* __restrict__ movers, long cap,
+                            const int* __restrict__ count_dev) {
+    long g = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    int lane = threadIdx.x % G;
+    if (g >= cap || g >= (long)*count_dev) return;
+    long dst = holes[g], src = movers[g];
+    if (dst < 0 || dst >= src || src >= R) return;
+    const unsigned* s = base + (u64)src * wpr;
+    unsigned* d = base + (u64)dst * wpr;
+    for (long j = lane; j < wpr; j += G) d[j] = s[j];
+}
+
+// Probe table rebuild after a removal: tk was filled with EMPTY; one thread
+// per surviving slot s < n' inserts (slot_keys[s], s) with a bounded-probe
+// CAS, like k_ht_rehash. The capacity is unchanged, so the load factor only
+// falls. n' comes from cnt (not from nrows_dev), and thread 0 publishes it
+// to nrows_dev, which no thread of this kernel reads.
+__global__ void k_ht_build(u64* __restrict__ tk, int* __restrict__ tv,
+                           long mask, const i64* __restrict__ slot_keys,
+                           long R, const int* __restrict__ cnt,
+                           int* __restrict__ nrows_dev) {
+    long s = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long np = (long)cnt[1];
+    if (s == 0) *nrows_dev = (int)np;
+    if (s >= np || s >= R) return;
+    u64 k = (u64)slot_keys[s];
+    if (k == EMPTY) return;
+    u64 h = splitmix64(k) & (u64)mask;
+    for (long p = 0; p <= mask; ++p) {
+        u64 prev = atomicCAS(&tk[h], EMPTY, k);
+        if (prev == EMPTY) { tv[h] = (int)s; return; }
+        h = (h + 1) & (u64)mask;
+    }
+}
+
+// array table: the flagged live rows stop being valid
+__global__ void k_expire_array(unsigned char* __restrict__ valid,
+                               const unsigned char* __restrict__ dead,
+                               long R) {
+    long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < R && dead[r]) valid[r] = 0;
+}
+
 // ============================================================== launchers
 
 // shared dispatch ladder of the plain and the bag-indirected reduce
@@ -3393,6 +3586,89 @@ void emb_delta_gather(const float* weights, const float* state, long R,
         k_delta_gather<64><<<grid1d(count * 64), BLOCK, 0, stream>>>(
             weights, state, R, dim, sd, slot_keys, shard_num, shard_id,
             slots, nslots, start, count, n_dev, keys_out, w_out, s_out);
+}
+
+void emb_expire_flag(const int* row_epoch, long R, int before,
+                     const int* nrows_dev, const unsigned char* valid,
+                     unsigned char* dead, hipStream_t stream) {
+    if (R)
+        k_expire_flag<<<grid1d(R), BLOCK, 0, stream>>>(row_epoch, R, before,
+                                                       nrows_dev, valid, dead);
+}
+
+void emb_flag_slots(const i64* slots, long n, unsigned char* dead, long R,
+                    hipStream_t stream) {
+    fill_u8(dead, R, 0, stream);
+    if (n && R)
+        k_flag_slots<<<grid1d(n), BLOCK, 0, stream>>>(slots, n, dead, R);
+}
+
+void emb_expire_count(int mode, const unsigned char* dead, long R,
+                      const int* nrows_dev, const unsigned char* valid,
+                      const int* cnt, int* tile_counts, hipStream_t stream) {
+    if (!R) return;
+    int T = (int)emb_delta_tiles(R);
+#define LAUNCH_XP_COUNT(M)                                                   \
+    k_expire_count<M><<<T, BLOCK, 0, stream>>>(dead, R, nrows_dev, valid,   \
+                                               cnt, tile_counts)
+    if (mode == XP_DEAD) LAUNCH_XP_COUNT(XP_DEAD);
+    else if (mode == XP_HOLE) LAUNCH_XP_COUNT(XP_HOLE);
+    else LAUNCH_XP_COUNT(XP_MOVER);
+#undef LAUNCH_XP_COUNT
+}
+
+void emb_expire_counts(const int* tile_incl, long T, const int* nrows_dev,
+                       long R, int* cnt, hipStream_t stream) {
+    k_expire_counts<<<1, 64, 0, stream>>>(tile_incl, T, nrows_dev, R, cnt);
+}
+
+void emb_expire_compact(int mode, const unsigned char* dead, long R,
+                        const int* nrows_dev, const unsigned char* valid,
+                        const int* cnt, const int* tile_incl, int* list,
+                        i64* keys_out, const i64* slot_keys, long shard_num,
+                        long shard_id, long out_cap, hipStream_t stream) {
+    if (!R || out_cap <= 0) return;
+    int T = (int)emb_delta_tiles(R);
+#define LAUNCH_XP_COMPACT(M)                                                 \
+    k_expire_compact<M><<<T, BLOCK, 0, stream>>>(                           \
+        dead, R, nrows_dev, valid, cnt, tile_incl, list, keys_out,          \
+        slot_keys, shard_num, shard_id, out_cap)
+    if (mode == XP_DEAD) LAUNCH_XP_COMPACT(XP_DEAD);
+    else if (mode == XP_HOLE) LAUNCH_XP_COMPACT(XP_HOLE);
+    else LAUNCH_XP_COMPACT(XP_MOVER);
+#undef LAUNCH_XP_COMPACT
+}
+
+void emb_move_rows(void* base, long R, long wpr, const int* holes,
+                   const int* movers, long cap, const int* count_dev,
+                   hipStream_t stream) {
+    if (cap <= 0 || !R || wpr <= 0) return;
+    unsigned* b = static_cast<unsigned*>(base);
+    if (wpr <= 2)
+        k_move_rows<1><<<grid1d(cap), BLOCK, 0, stream>>>(
+            b, R, wpr, holes, movers, cap, count_dev);
+    else if (wpr <= 32)
+        k_move_rows<16><<<grid1d(cap * 16), BLOCK, 0, stream>>>(
+            b, R, wpr, holes, movers, cap, count_dev);
+    else
+        k_move_rows<64><<<grid1d(cap * 64), BLOCK, 0, stream>>>(
+            b, R, wpr, holes, movers, cap, count_dev);
+}
+
+// rows: a host bound of n' that sizes the grid (at least one thread runs,
+// to publish n')
+void emb_ht_build(u64* tk, int* tv, long cap, const i64* slot_keys, long R,
+                  const int* cnt, int* nrows_dev, long rows,
+                  hipStream_t stream) {
+    fill_u64(tk, cap, EMPTY, stream);
+    k_ht_build<<<grid1d(rows > 0 ? rows : 1), BLOCK, 0, stream>>>(
+        tk, tv, cap - 1, slot_keys, R, cnt, nrows_dev);
+}
+
+void emb_expire_array(unsigned char* valid, const unsigned char* dead, long R,
+                      hipStream_t stream) {
+    if (R)
+        k_expire_array<<<grid1d(R), BLOCK, 0, stream>>>(valid, dead, R);
 }
 
 void emb_fault_in(const i64* keys, long n, const int* u_dev, const u64* htk,

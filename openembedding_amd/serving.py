@@ -30,7 +30,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from .checkpoint import iter_blocks, read_meta
+from .checkpoint import iter_blocks, iter_removed, read_meta
 from .core.variable import VariableMeta, VariableShard
 
 
@@ -245,13 +245,31 @@ class ServedModel:
             rows += len(keys)
         return rows
 
+    def _remove(self, uri: str, meta: dict, shards: dict):
+        """Apply a delta's tombstones through each shard's ``remove_rows``;
+        returns the number of rows that went, None for a delta without
+        tombstones."""
+        gone = None
+        for hdr, keys in iter_removed(uri, meta):
+            gone = gone or 0
+            sh = shards.get(hdr["variable_id"])
+            if sh is None or not len(keys):
+                continue
+            kt = torch.from_numpy(keys.copy()).to(sh.device)
+            gone += int(sh.remove_rows(kt).numel())
+        return gone
+
     def apply_delta(self, uri: str) -> dict:
-        """Upsert a delta checkpoint into the live tables, whatever their
-        row format: each row goes through the shard's ``import_rows``, which
-        overwrites an existing key and, on a quantized table, quantizes the
-        row into place. Refused with RuntimeError, before anything changes,
-        unless the delta continues this model's chain
-        (``checkpoint.check_delta``).
+        """Apply a delta checkpoint to the live tables, whatever their row
+        format: first its tombstones (the keys removed by the trainer's
+        expiry) through the shard's ``remove_rows``, then its rows through
+        ``import_rows``, which overwrites an existing key and, on a
+        quantized table, quantizes the row into place. A key that expired
+        and came back inside the interval is in both lists and survives.
+        Refused with RuntimeError, before anything changes, unless the
+        delta continues this model's chain (``checkpoint.check_delta``).
+        The result of a delta that carries tombstones has a ``"removed"``
+        count beside ``since``, ``epoch`` and ``rows``.
 
         A block that a quantized table cannot hold (``ValueError`` from its
         ``import_rows``: a non-finite value, an fp16 overflow) stops the
@@ -263,9 +281,12 @@ class ServedModel:
         one quantizing kernel, and a read that overlaps the update may see
         rows and variables of both epochs, may miss a key that the update
         is creating (a table that grows swaps its buffers), and on a CPU
-        table may even catch a row mid-copy. A caller that needs a
-        consistent view quiesces reads around the call or updates a second
-        replica and switches. Updates of one model are serialized."""
+        table may even catch a row mid-copy. A removal moves the last rows
+        of a hash table into the holes and rebuilds its key map: a read
+        that overlaps it may miss any key of the table for a moment, or
+        briefly resolve a key to a slot whose row has moved. A caller that
+        needs a consistent view quiesces reads around the call or updates a
+        second replica and switches. Updates of one model are serialized."""
         from .checkpoint import check_delta
         with self._update_lock:
             if self.status != ModelStatus.NORMAL:
@@ -281,11 +302,16 @@ class ServedModel:
                         f"delta variable {mvar['variable_id']} does not "
                         "match the loaded model")
             try:
+                removed = self._remove(uri, meta, shards)
                 rows = self._import(uri, meta, shards, update=True)
             finally:
                 self._export_cache = {}  # replica pages must show the update
             self.loaded_epoch = d["epoch"]
-        return {"since": d["since"], "epoch": d["epoch"], "rows": rows}
+            out = {"since": d["since"], "epoch": d["epoch"], "rows": rows}
+            if removed is not None:
+                out["removed"] = removed
+            self.last_update = out
+        return out
 
     def export_block(self, variable_id: int, start: int, count: int):
         """Row block [start, start+count) of a variable in export order —
@@ -691,7 +717,8 @@ def make_app(controller: Optional[ModelController] = None,
     @app.post("/models/{sign}/deltas")
     def update_model(sign: str, req: UpdateModelReq):
         """Apply a delta checkpoint to a live model; answers with the
-        model's description at the new epoch. 404 unknown sign, 409 a delta
+        model's description at the new epoch, with the ``removed`` count of
+        a delta that carried tombstones. 404 unknown sign, 409 a delta
         that does not continue the chain, 400 an unreadable URI, 422 rows
         that the table's format cannot hold (the blocks before them stay
         applied, the epoch does not move)."""
@@ -705,7 +732,11 @@ def make_app(controller: Optional[ModelController] = None,
             raise HTTPException(status_code=400, detail=str(e))
         except RuntimeError as e:
             raise HTTPException(status_code=409, detail=str(e))
-        return m.describe()
+        out = m.describe()
+        last = getattr(m, "last_update", None) or {}
+        if "removed" in last:
+            out["removed"] = last["removed"]
+        return out
 
     @app.get("/models/{sign}/variables/{variable_id}/rows")
     def export_rows(sign: str, variable_id: int, start: int = 0,

@@ -37,7 +37,8 @@ __all__ = [
     "distributed_optimizer", "DistributedOptimizer", "distributed_model",
     "Model", "save_server_model", "load_server_model",
     "track_server_model_changes", "save_server_model_delta",
-    "load_server_model_delta", "save_as_original_model", "pulling", "sparse_read_as_dense",
+    "load_server_model_delta", "expire_server_model",
+    "save_as_original_model", "pulling", "sparse_read_as_dense",
     "should_persist_server_model", "persist_server_model",
     "restore_server_model", "get_context",
     "Adadelta", "Adagrad", "Adam", "Adamax", "Ftrl", "Nadam", "NAdam",
@@ -984,6 +985,34 @@ def load_server_model_delta(path: str) -> dict:
     (``checkpoint.apply_delta``)."""
     from ..checkpoint import apply_delta
     return apply_delta(get_context(), path)
+
+
+def expire_server_model(max_age: Optional[int] = None,
+                        before: Optional[int] = None) -> dict:
+    """Drop, in place, the rows of every variable that were last written
+    before epoch ``before`` (default: the current epoch minus ``max_age``;
+    give exactly one). The epoch advances at every save of either kind, and
+    training writes every pulled row at commit, so ``max_age=3`` drops the
+    ids not seen during the last three save intervals. Needs
+    ``track_server_model_changes()``; the next ``save_server_model_delta``
+    tells the replicas which keys went. Every rank calls it. Returns
+    ``{"before", "rows"}`` (rows removed on this rank).
+
+    Contract: call it between ``opt.step()`` and the next forward. Rows move
+    between slots, so pull handles held across the call — by autograd (a
+    forward without its backward and step) or by a prefetch — are invalid.
+    Refused with RuntimeError while any variable holds prefetched pulls or
+    uncommitted gradients. A dropped id that shows up again starts from its
+    initial row."""
+    for e in _tracked_live():
+        v = getattr(e, "variable", None)
+        if v is not None and v._prefetched:
+            raise RuntimeError(
+                "expire_server_model with prefetched pulls outstanding: "
+                "their handles name slots that the expiry moves. Consume "
+                "them (forward, backward, step) first")
+    from ..checkpoint import expire_rows
+    return expire_rows(get_context(), max_age=max_age, before=before)
 
 
 def save_as_original_model(model: nn.Module, path: str,
