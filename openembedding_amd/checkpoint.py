@@ -33,6 +33,16 @@ shard's ``remove_rows``) travel as tombstones: per storage and rank that has
 any, a file ``removed_<rank>`` of sections {header with ``"removed": true``,
 blocks of {n, keys[n]}}. ``apply_delta`` removes first and upserts second,
 so a key that expired and came back inside the interval survives.
+
+Admission filters (``shard.set_admission``): every section header records the
+variable's ``"admission": {min_count, width, depth, seed}`` (absent while
+off), and a full dump writes, per storage and rank that has any, a file
+``admission_<rank>`` of sections {header with ``"admission"``, ``shard_id``,
+``shard_num`` and ``num_counters``, then the raw little-endian int32 sketch}.
+A delta writes no such file. ``load_model`` restores settings and sketch
+exactly at the saved shard count; at another one every shard loads the
+element-wise sum of the saved sketches, which is the sketch of the joined
+stream: it over-counts, so no id is admitted later than it would have been.
 """
 
 from __future__ import annotations
@@ -40,6 +50,7 @@ from __future__ import annotations
 import json
 import os
 import struct
+import warnings
 from typing import Optional
 
 import numpy as np
@@ -65,7 +76,16 @@ def _var_header(var, include_optimizer: bool) -> dict:
                         **shard.initializer.dump_config()},
         "shard_id": shard.shard_id,
         "shard_num": shard.shard_num,
+        # "admission" only while a filter is on: without one a header is
+        # byte for byte what it was before admission existed
+        **({"admission": _admission_cfg(shard)}
+           if _admission_cfg(shard) is not None else {}),
     }
+
+
+def _admission_cfg(shard) -> Optional[dict]:
+    a = getattr(shard, "_admit", None)
+    return dict(a) if a is not None else None
 
 
 def _shards(ctx):
@@ -107,6 +127,7 @@ def dump_model(ctx, uri: str, include_optimizer: bool = True) -> None:
         meta["epoch"] = epoch
         meta["model_uuid"] = ctx.model_uuid
     _write_dump(ctx, uri, meta, include_optimizer, None)
+    _write_admission(ctx, uri)
     if epoch is not None:
         _advance(ctx, epoch + 1)
         # a full dump is a state any consumer can reload: the removals
@@ -220,6 +241,94 @@ def _write_removed(ctx, uri: str, since: int) -> None:
             if f is not None:
                 f.close()
     ctx.barrier()
+
+
+def _write_admission(ctx, uri: str) -> None:
+    """The admission sketches of a full dump: ``<storage>/admission_<rank>``
+    with one section per variable whose filter is on."""
+    for st in ctx.storages:
+        f = None
+        try:
+            for var in st.variables:
+                sh = var.shard
+                cfg = _admission_cfg(sh)
+                if cfg is None:
+                    continue
+                sketch = sh.export_admission().cpu().numpy().astype("<i4")
+                if f is None:
+                    f = open(os.path.join(uri, str(st.storage_id),
+                                          f"admission_{ctx.rank}"), "wb")
+                _write_header(f, {"variable_id": sh.meta.variable_id,
+                                  "admission": cfg, "shard_id": sh.shard_id,
+                                  "shard_num": sh.shard_num,
+                                  "num_counters": int(sketch.size)})
+                f.write(sketch.tobytes())
+        finally:
+            if f is not None:
+                f.close()
+    ctx.barrier()
+
+
+def iter_admission(uri: str, meta: Optional[dict] = None):
+    """Stream the admission sketches of a full dump: yields (header_dict,
+    sketch <i4 [depth * width]) per section of every ``admission_<rank>``
+    file. Nothing for a dump without them."""
+    meta = meta or read_meta(uri)
+    for st_ord in range(meta["num_storages"]):
+        d = os.path.join(uri, str(st_ord))
+        for fname in sorted(os.listdir(d)):
+            if not fname.startswith("admission_"):
+                continue
+            with open(os.path.join(d, fname), "rb") as f:
+                while True:
+                    magic = f.read(8)
+                    if not magic:
+                        break
+                    if magic != MAGIC:
+                        raise RuntimeError(f"bad admission file {fname}")
+                    (hlen,) = struct.unpack("<q", f.read(8))
+                    hdr = json.loads(f.read(hlen))
+                    yield hdr, np.frombuffer(
+                        f.read(hdr["num_counters"] * 4), dtype="<i4")
+
+
+def _load_admission(ctx, uri: str, meta: dict, by_id: dict) -> None:
+    """Restore the admission filters of a full dump (module docstring). A
+    dump without admission files leaves every filter as it is."""
+    saved = {}
+    for hdr, sketch in iter_admission(uri, meta):
+        if hdr["variable_id"] in by_id:
+            saved.setdefault(hdr["variable_id"], []).append((hdr, sketch))
+    for vid, parts in saved.items():
+        shard = by_id[vid].shard
+        if getattr(shard, "set_admission", None) is None:
+            continue   # a read-only table: a miss is a zero row already
+        cfg = parts[0][0]["admission"]
+        geometry = {tuple(h["admission"][k] for k in ("width", "depth",
+                                                      "seed"))
+                    for h, _ in parts}
+        try:
+            shard.set_admission(**cfg)
+        except NotImplementedError as e:
+            warnings.warn(f"variable {vid}: admission filter of the dump "
+                          f"not restored ({e})")
+            continue
+        mine = [sk for h, sk in parts
+                if h["shard_num"] == shard.shard_num
+                and h["shard_id"] == shard.shard_id]
+        if len(mine) == 1 and len(parts) == shard.shard_num:
+            shard.import_admission(torch.from_numpy(mine[0].copy()))
+        elif len(geometry) == 1:
+            total = np.zeros(parts[0][1].size, dtype=np.int64)
+            for _, sk in parts:
+                total += sk
+            total = np.minimum(total, np.iinfo(np.int32).max).astype("<i4")
+            shard.import_admission(torch.from_numpy(total))
+        else:
+            warnings.warn(f"variable {vid}: the dump's admission sketches "
+                          "differ in width, depth or seed and cannot be "
+                          "summed; the filter starts empty")
+            shard.age_admission(31)
 
 
 def _model_meta(ctx) -> dict:
@@ -355,6 +464,13 @@ def _apply_config(var, hdr: dict) -> None:
         cur = var.shard.optimizer
         if cur is None or cur.category != cat or cur.dump_config() != c:
             var.shard.set_optimizer(cat, **c)
+    adm = hdr.get("admission")
+    if adm and getattr(var.shard, "set_admission", None) is not None:
+        try:
+            var.shard.set_admission(**adm)   # keeps counters of equal shape
+        except NotImplementedError as e:
+            warnings.warn(f"variable {hdr['variable_id']}: admission filter "
+                          f"of the dump not restored ({e})")
 
 
 def read_meta(uri: str) -> dict:
@@ -446,6 +562,7 @@ def load_model(ctx, uri: str) -> None:
     for mvar in meta["variables"]:
         by_id[mvar["variable_id"]].shard.clear()
     _import_blocks(ctx, uri, meta, by_id)
+    _load_admission(ctx, uri, meta, by_id)
     ctx.loaded_epoch = meta.get("epoch")
     ctx.loaded_model_uuid = meta.get("model_uuid")
     if tracked_epoch(ctx) is not None:

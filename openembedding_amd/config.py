@@ -16,6 +16,9 @@ config strings keep working) but unused, and say so in their help. The
   server.update_early_return -> commit on a side stream (overlap analogue)
   server.track_changes    -> new variables record which rows change, for
                              delta checkpoints (checkpoint.dump_delta)
+  server.admission_min_count -> new untiered hash variables start with an
+                             admission filter of this min_count
+                             (VariableShard.set_admission); 0 = off
 """
 
 from __future__ import annotations
@@ -87,6 +90,8 @@ class ServerConfig:
     pmem_pool_root_path: str = ""         # host-DRAM tier spill dir analogue
     track_changes: bool = False           # variables start with change
                                           # tracking on (delta checkpoints)
+    admission_min_count: int = 0          # new hash variables admit a key
+                                          # after this many sightings; 0 = off
 
     @classmethod
     def parse(cls, cfg: Dict[str, Any]) -> "ServerConfig":

@@ -175,6 +175,9 @@ class Context:
                           device=str(self.device), seed=self.seed, **kw)
         if self.config.server.track_changes:
             shard.track_changes(True)
+        if (self.config.server.admission_min_count > 0
+                and meta.use_hash_table and cache_mb <= 0):
+            shard.set_admission(self.config.server.admission_min_count)
         var = ShardedVariable(shard, storage)
         self.variables[vid] = var
         return var

@@ -369,6 +369,13 @@ class HipTieredVariableShard(HipVariableShard):
                 "moves rows between slots on eviction: delta checkpoints "
                 "need an untiered variable (server.cache_size_mb = 0)")
 
+    def set_admission(self, min_count, *args, **kw) -> None:
+        if min_count:
+            raise NotImplementedError(
+                "the capacity tier treats a cache miss as a fault-in from "
+                "the host tier, not as a first sighting: admission needs an "
+                "untiered variable (server.cache_size_mb = 0)")
+
     def expire_rows(self, before: int):
         raise NotImplementedError(
             "row expiry rewrites the slab in place and the capacity tier "

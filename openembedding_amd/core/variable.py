@@ -230,14 +230,145 @@ class VariableShard:
                             slots, torch.full_like(slots, -1))
         return slots
 
+    # --------------------------------------------------------------- admission
+    # A count-min filter in front of a hashed row's creation: a key earns its
+    # row once it was seen ``min_count`` times. A sighting is one training
+    # pull that contains the key and misses the table; keys reach a pull
+    # unique, so this counts steps seen, not occurrences, and a layer called
+    # twice in a step counts twice. Read-only pulls never count. Until a key
+    # is admitted its slot is -1: the pull reads a zero row, its gradient is
+    # dropped and nothing is created. The estimate only over-counts, so a key
+    # is never admitted late, only sometimes early. With the filter on every
+    # commit-time lookup is read-only (a push is no sighting), while
+    # import_rows inserts unconditionally (a saved row was admitted once).
+    # Removed rows keep their counters: an expired key comes back at its next
+    # sighting unless the sketch was aged. Counters are int32 and never
+    # saturate on their own; ``age_admission`` is what keeps an endless
+    # stream from filling the sketch. This torch form is the CPU path and
+    # the oracle of the HIP kernels.
+
+    _admit: Optional[dict] = None  # settings while the filter is on
+
+    def set_admission(self, min_count: Optional[int], width: int = 1 << 22,
+                      depth: int = 4, seed: Optional[int] = None) -> None:
+        """Turn the admission filter on, with an empty sketch of ``depth``
+        rows of ``width`` int32 counters, or off (``min_count`` 0 or None;
+        frees the sketch). ``seed`` defaults to the variable's. Setting the
+        same width, depth and seed again keeps the counters."""
+        if not min_count:
+            self._admit = None
+            for name in ("admit_sketch", "admit_stats"):
+                self.__dict__.pop(name, None)
+            return
+        if not self.meta.use_hash_table:
+            raise ValueError("admission needs a hash table: an array "
+                             "table's rows are preallocated")
+        min_count, width, depth = int(min_count), int(width), int(depth)
+        if min_count < 1 or min_count >= 1 << 31:
+            raise ValueError("min_count must be a positive int32")
+        if width < 1 or width & (width - 1):
+            raise ValueError("width must be a power of two")
+        if not 1 <= depth <= 8:
+            raise ValueError("depth must be in 1..8")
+        seed = self.seed if seed is None else int(seed)
+        seed = ((seed + (1 << 63)) % (1 << 64)) - (1 << 63)  # as int64
+        old = self._admit
+        self._admit = {"min_count": min_count, "width": width,
+                       "depth": depth, "seed": seed}
+        if old is not None and all(old[k] == self._admit[k]
+                                   for k in ("width", "depth", "seed")):
+            return
+        self.admit_sketch = torch.zeros(depth * width, dtype=torch.int32,
+                                        device=self.device)
+        self.admit_stats = torch.zeros(2, dtype=torch.int64,
+                                       device=self.device)
+
+    def _need_admission(self) -> dict:
+        if self._admit is None:
+            raise RuntimeError("admission is off: call set_admission() first")
+        return self._admit
+
+    def age_admission(self, shift: int = 1) -> None:
+        """Every counter ``>> shift``; ``shift >= 31`` empties the sketch."""
+        from ..ops import dispatch as ops
+        self._need_admission()
+        ops.admit_age(self.admit_sketch, shift)
+
+    def admission_stats(self) -> dict:
+        """{min_count, width, depth, admitted, turned_away, fill}; fill is
+        the share of nonzero counters. All zero while the filter is off."""
+        a = self._admit
+        if a is None:
+            return {"min_count": 0, "width": 0, "depth": 0, "admitted": 0,
+                    "turned_away": 0, "fill": 0.0}
+        adm, away = self.admit_stats.tolist()
+        fill = float((self.admit_sketch != 0).sum()) / self.admit_sketch.numel()
+        return {"min_count": a["min_count"], "width": a["width"],
+                "depth": a["depth"], "admitted": int(adm),
+                "turned_away": int(away), "fill": fill}
+
+    def export_admission(self) -> Optional[torch.Tensor]:
+        """A copy of the sketch (int32 [depth * width]); None while off."""
+        if self._admit is None:
+            return None
+        return self.admit_sketch.clone()
+
+    def import_admission(self, sketch: torch.Tensor, add: bool = False
+                         ) -> None:
+        """Replace the sketch by ``sketch`` or, with ``add``, add to it
+        element-wise (the sum of two sketches with equal hashes is the
+        sketch of the joined stream)."""
+        self._need_admission()
+        sketch = sketch.to(self.device, torch.int32).reshape(-1)
+        if sketch.numel() != self.admit_sketch.numel():
+            raise ValueError("sketch does not hold depth * width counters")
+        if add:
+            self.admit_sketch += sketch
+        else:
+            self.admit_sketch.copy_(sketch)
+
+    def _lookup_pull(self, keys: torch.Tensor, *bounded):
+        """``_lookup_or_insert`` as a training pull reaches it: through the
+        admission filter when that is on."""
+        if self._admit is None:
+            return self._lookup_or_insert(keys, *bounded)
+        return self._lookup_admit(keys, *bounded)
+
+    def _lookup_admit(self, keys: torch.Tensor):
+        from ..ops import dispatch as ops
+        a = self._admit
+        if bool((keys == -1).any()):
+            raise ValueError("key -1 is reserved in hash mode (table empty "
+                             "marker; same reservation as the reference)")
+        slots = self._lookup_readonly(keys)
+        new_mask = torch.zeros(keys.numel(), dtype=torch.bool,
+                               device=self.device)
+        miss = (slots < 0).nonzero(as_tuple=True)[0]
+        if miss.numel():
+            est = ops.admit_note(self.admit_sketch, keys[miss], a["depth"],
+                                 a["seed"])
+            ok = miss[est >= a["min_count"]]
+            if ok.numel():
+                slots[ok], new_mask[ok] = self._lookup_or_insert(keys[ok])
+            self.admit_stats[0] += ok.numel()
+            self.admit_stats[1] += miss.numel() - ok.numel()
+        return slots, new_mask
+
     # ---------------------------------------------------------------- training
 
     def pull(self, keys: torch.Tensor) -> torch.Tensor:
         """keys: unique int64 [n] owned by this shard -> weights [n, dim].
         Missing rows are created and initialized (reference
-        EmbeddingOptimizerVariable.h:242-266)."""
-        slots, _ = self._lookup_or_insert(keys)
-        return self.weights[slots].clone()
+        EmbeddingOptimizerVariable.h:242-266). With an admission filter a
+        key that has not earned its row yet reads as a zero row."""
+        slots, _ = self._lookup_pull(keys)
+        if self._admit is None:
+            return self.weights[slots].clone()
+        out = torch.zeros((keys.numel(), self.dim), dtype=self.dtype,
+                          device=self.device)
+        hit = slots >= 0
+        out[hit] = self.weights[slots[hit]]
+        return out
 
     def pull_readonly(self, keys: torch.Tensor) -> torch.Tensor:
         """Serving-mode pull: missing rows come back zero, table untouched
@@ -295,7 +426,14 @@ class VariableShard:
             c.index_add_(0, inv, counts)
             keys, grads, counts = uk, g, c
         self._pending = []
-        slots, _ = self._lookup_or_insert(keys)
+        if self._admit is None:
+            slots, _ = self._lookup_or_insert(keys)
+        else:
+            # a push is no sighting: a key without a row is dropped
+            slots = self._lookup_readonly(keys)
+            hit = slots >= 0
+            keys, grads, counts, slots = (keys[hit], grads[hit], counts[hit],
+                                          slots[hit])
         w = self.weights[slots]
         s = self.state[slots]
         self.optimizer.update(w, s, counts, grads)

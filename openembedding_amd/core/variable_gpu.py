@@ -162,6 +162,23 @@ class HipVariableShard(VariableShard):
         self._reserved_rows = rows
 
     def _lookup_or_insert(self, keys: torch.Tensor, u_dev=None):
+        return self._insert_lookup(keys, u_dev, False)
+
+    def _lookup_admit(self, keys: torch.Tensor, u_dev=None):
+        return self._insert_lookup(keys, u_dev, True)
+
+    def set_admission(self, min_count, width: int = 1 << 22, depth: int = 4,
+                      seed=None) -> None:
+        if self._in_graph_capture():
+            raise RuntimeError("the admission sketch cannot be (re)allocated "
+                               "under stream capture")
+        super().set_admission(min_count, width, depth, seed)
+
+    def _insert_lookup(self, keys: torch.Tensor, u_dev, admit: bool):
+        """Lookup that may insert. ``admit`` puts the count-min filter in
+        front of the insert (two launches, ``ht_lookup_admit``); capacity is
+        kept for all n keys either way, so the row bound stays an upper
+        bound."""
         n = keys.numel()
         if self.meta.use_hash_table:
             if self._in_graph_capture():
@@ -178,9 +195,16 @@ class HipVariableShard(VariableShard):
                 self._ensure_rows(self._nrows_upper + n)
                 self._maybe_rehash()
                 self._nrows_upper += n
-            slots, new_mask = self.ext.ht_lookup(self.tk, self.tv, keys,
-                                                 self.nrows_dev, self.slot_keys,
-                                                 True, u_dev)
+            if admit:
+                a = self._admit
+                slots, new_mask = self.ext.ht_lookup_admit(
+                    self.tk, self.tv, keys, self.nrows_dev, self.slot_keys,
+                    self.admit_sketch, a["depth"], a["seed"], a["min_count"],
+                    self.admit_stats, u_dev)
+            else:
+                slots, new_mask = self.ext.ht_lookup(
+                    self.tk, self.tv, keys, self.nrows_dev, self.slot_keys,
+                    True, u_dev)
         else:
             slots, new_mask = self.ext.array_touch(self.valid_u8, keys,
                                                    self.shard_num, u_dev)
@@ -227,7 +251,7 @@ class HipVariableShard(VariableShard):
                                     sir.reshape(-1), want_out, u_dev)
 
     def pull(self, keys: torch.Tensor) -> torch.Tensor:
-        slots, new_mask = self._lookup_or_insert(keys)
+        slots, new_mask = self._lookup_pull(keys)
         return self._gather(keys, slots, new_mask, True)
 
     def pull_bounded(self, keys_buf: torch.Tensor, u_dev: torch.Tensor,
@@ -235,7 +259,7 @@ class HipVariableShard(VariableShard):
         """Sync-free pull: keys_buf is an n-sized unique buffer with the live
         count in u_dev (device int32); the gather iterates the full inverse
         and fuses the duplicate scatter. Returns (out [n_elems, dim], slots)."""
-        slots, new_mask = self._lookup_or_insert(keys_buf, u_dev)
+        slots, new_mask = self._lookup_pull(keys_buf, u_dev)
         out = self._gather(keys_buf, slots, new_mask, True,
                            inverse=inverse, u_dev=u_dev)
         return out, slots
@@ -258,7 +282,7 @@ class HipVariableShard(VariableShard):
         index = tuple(r[3:8])
         slot_of, tv, toff, rank, slots, new_mask = r[8:14]
         if hash_mode:
-            slots, new_mask = self._lookup_or_insert(uk, u_dev)
+            slots, new_mask = self._lookup_pull(uk, u_dev)
         cat, p0, p1, p2 = _init_params(self.initializer)
         sir = self._state_init_row
         if sir is None:
@@ -283,7 +307,7 @@ class HipVariableShard(VariableShard):
         exists. Returns (out [B, dim], slots, bag_of [nnz]); with
         per-sample ``weights`` (float32 [nnz]) the weighted pool runs
         instead and its bag_scale [B] is returned as a fourth value."""
-        slots, new_mask = self._lookup_or_insert(keys_buf, u_dev)
+        slots, new_mask = self._lookup_pull(keys_buf, u_dev)
         self._gather(keys_buf, slots, new_mask, False, u_dev=u_dev)
         if weights is not None:
             out, bag_of, bag_scale = self.ext.pool_fwd_weighted(
@@ -408,9 +432,10 @@ class HipVariableShard(VariableShard):
                                      device=self.device)
                 counts.index_add_(0, inv, counts0)
             self._pending = []
-            slots, new_mask = self._lookup_or_insert(keys)
-            # init rows that were pushed without a prior pull
-            self._gather(keys, slots, new_mask, False)
+            slots, new_mask = self._lookup_commit(keys)
+            if new_mask is not None:
+                # init rows that were pushed without a prior pull
+                self._gather(keys, slots, new_mask, False)
             self._apply(opt_id, slots, grads, counts, cfg, None)
         if self.meta.use_hash_table and not self._in_graph_capture():
             # every 16 commits: tighten the row-count bound (the D2H read
@@ -440,10 +465,22 @@ class HipVariableShard(VariableShard):
         g2c, _ = self.ext.reduce_by_inverse(inv, payload.contiguous(),
                                             keys.numel())
         g2, c2 = self.ext.split_payload(g2c, u_dev)
-        slots, new_mask = self._lookup_or_insert(uk, u_dev)
-        # init rows that were pushed without a prior pull
-        self._gather(uk, slots, new_mask, False, u_dev=u_dev)
+        slots, new_mask = self._lookup_commit(uk, u_dev)
+        if new_mask is not None:
+            # init rows that were pushed without a prior pull
+            self._gather(uk, slots, new_mask, False, u_dev=u_dev)
         return uk, u_dev, slots, g2, c2
+
+    def _lookup_commit(self, keys: torch.Tensor, u_dev=None):
+        """The lookup of a commit: (slots, new_mask). With an admission
+        filter it is read-only, since a push is no sighting: a pushed key
+        without a row keeps slot -1, which the apply kernels skip, and
+        new_mask is None."""
+        if self._admit is None:
+            return self._lookup_or_insert(keys, u_dev)
+        slots, _ = self.ext.ht_lookup(self.tk, self.tv, keys, self.nrows_dev,
+                                      self.slot_keys, False, u_dev)
+        return slots, None
 
     @staticmethod
     def _in_graph_capture() -> bool:

@@ -53,6 +53,10 @@ void emb_ht_lookup(u64*, int*, long, const i64*, long, int*, i64*, i64*,
                    unsigned char*, int, const int*, long, hipStream_t_);
 void emb_ht_rehash(const u64*, const int*, long, u64*, int*, long,
                    hipStream_t_);
+void emb_ht_lookup_admit(u64*, int*, long, const i64*, long, int*, i64*, long,
+                         int*, long, int, u64, int, u64*, i64*,
+                         unsigned char*, const int*, hipStream_t_);
+void emb_admit_age(int*, long, int, hipStream_t_);
 void emb_array_touch(unsigned char*, const i64*, long, long, long, i64*,
                      unsigned char*, const int*, hipStream_t_);
 void emb_gather_init(float*, float*, long, long, const i64*,
@@ -452,6 +456,64 @@ std::tuple<torch::Tensor, torch::Tensor> ht_lookup(
                       insert ? 1 : 0, u_ptr(u_dev), slot_keys.numel(),
                       cur_stream());
     return {slots, new_mask};
+}
+
+// ---- feature admission ---------------------------------------------------
+// ht_lookup(insert = true) behind a count-min filter (embops.hip, "feature
+// admission"): a key that misses adds one sighting to ``sketch`` (int32
+// [depth * width], width a power of two) and is inserted only when its
+// estimate reaches ``min_count``; otherwise its slot is -1. ``stats`` (int64
+// [2]) gains the admitted and the turned-away sightings.
+
+void check_sketch(const torch::Tensor& sketch, int64_t depth) {
+    CHECK_GPU(sketch); CHECK_CONT(sketch);
+    TORCH_CHECK(sketch.dtype() == torch::kInt32, "sketch must be int32");
+    TORCH_CHECK(depth >= 1 && depth <= 8, "depth must be in 1..8");
+    long W = sketch.numel() / depth;
+    TORCH_CHECK(W >= 1 && W * depth == sketch.numel() && (W & (W - 1)) == 0,
+                "sketch must hold depth rows of a power-of-two width");
+}
+
+std::tuple<torch::Tensor, torch::Tensor> ht_lookup_admit(
+    torch::Tensor tk, torch::Tensor tv, torch::Tensor keys,
+    torch::Tensor nrows, torch::Tensor slot_keys, torch::Tensor sketch,
+    int64_t depth, int64_t seed, int64_t min_count, torch::Tensor stats,
+    OptTensor u_dev) {
+    CHECK_GPU(keys); CHECK_CONT(keys);
+    TORCH_CHECK(keys.dtype() == torch::kInt64);
+    check_sketch(sketch, depth);
+    CHECK_GPU(stats); CHECK_CONT(stats);
+    TORCH_CHECK(stats.dtype() == torch::kInt64 && stats.numel() == 2,
+                "stats must be int64 [2]");
+    TORCH_CHECK(min_count >= 1 && min_count <= INT32_MAX,
+                "min_count must be a positive int32");
+    const c10::cuda::CUDAGuard guard(keys.device());
+    long n = keys.numel();
+    auto slots = torch::empty({n}, keys.options());
+    auto new_mask = torch::empty({n}, keys.options().dtype(torch::kUInt8));
+    if (n)
+        emb_ht_lookup_admit((u64*)tk.data_ptr<i64>(), tv.data_ptr<int>(),
+                            tk.numel(), keys.data_ptr<i64>(), n,
+                            nrows.data_ptr<int>(), slot_keys.data_ptr<i64>(),
+                            slot_keys.numel(), sketch.data_ptr<int>(),
+                            sketch.numel() / depth, (int)depth, (u64)seed,
+                            (int)min_count, (u64*)stats.data_ptr<i64>(),
+                            slots.data_ptr<i64>(),
+                            new_mask.data_ptr<uint8_t>(), u_ptr(u_dev),
+                            cur_stream());
+    return {slots, new_mask};
+}
+
+// every counter >> shift in place; shift >= 31 zeroes the sketch
+void admit_age(torch::Tensor sketch, int64_t shift) {
+    CHECK_GPU(sketch); CHECK_CONT(sketch);
+    TORCH_CHECK(sketch.dtype() == torch::kInt32, "sketch must be int32");
+    TORCH_CHECK(shift >= 0, "shift must not be negative");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(sketch.data_ptr()) % 16 == 0,
+                "sketch must be 16-byte aligned");
+    const c10::cuda::CUDAGuard guard(sketch.device());
+    emb_admit_age(sketch.data_ptr<int>(), sketch.numel(),
+                  (int)(shift > 31 ? 31 : shift), cur_stream());
 }
 
 void ht_rehash(torch::Tensor tk_old, torch::Tensor tv_old, torch::Tensor tk_new,
@@ -2264,6 +2326,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("field_offsets") = pybind11::none());
     m.def("ht_lookup", &ht_lookup, "hash table lookup/insert");
     m.def("ht_rehash", &ht_rehash, "hash table rehash into larger table");
+    m.def("ht_lookup_admit", &ht_lookup_admit,
+          "hash table lookup/insert behind a count-min admission filter",
+          pybind11::arg("tk"), pybind11::arg("tv"), pybind11::arg("keys"),
+          pybind11::arg("nrows"), pybind11::arg("slot_keys"),
+          pybind11::arg("sketch"), pybind11::arg("depth"),
+          pybind11::arg("seed"), pybind11::arg("min_count"),
+          pybind11::arg("stats"), pybind11::arg("u_dev") = pybind11::none());
+    m.def("admit_age", &admit_age,
+          "arithmetic right shift of every admission counter, in place");
     m.def("array_touch", &array_touch,
           "array-table slot compute + valid-bitmap touch");
     m.def("gather_init", &gather_init,

@@ -475,6 +475,45 @@ __global__ void k_unique_inverse(long n, const int* __restrict__ slot_of,
 // written by an insert in an earlier kernel is visible (kernel-boundary
 // ordering), no spin needed.
 
+// The probe / insert loop of one key (never EMPTY), shared by k_ht_lookup
+// and the admission kernels below. Returns the slot, -1 for a miss; is_new
+// is set when this call created the row.
+DEV i64 ht_probe(u64* __restrict__ tk, int* __restrict__ tv, long mask,
+                 u64 k, int insert, int* __restrict__ nrows,
+                 i64* __restrict__ slot_keys, long row_cap,
+                 unsigned char& is_new) {
+    u64 h = splitmix64(k) & (u64)mask;
+    i64 slot = -1;
+    is_new = 0;
+    // bounded probe: a full table (host sizing bug) yields slot -1 (miss)
+    // instead of hanging the GPU
+    for (long p = 0; p <= mask; ++p) {
+        u64 cur = tk[h];
+        if (cur == k) { slot = (i64)tv[h]; break; }
+        if (cur == EMPTY) {
+            if (!insert) { slot = -1; break; }
+            u64 prev = atomicCAS(&tk[h], EMPTY, k);
+            if (prev == EMPTY) {
+                int s = atomicAdd(nrows, 1);
+                if (s >= row_cap) {  // slab full (host sizing bug or a
+                    tv[h] = -1;      // graph-captured insert): this call AND
+                    slot = -1;       // every later lookup of this key must
+                    break;           // see a miss — a never-written tv[h]
+                }                    // here would later read as a garbage
+                                     // slot index (OOB row access)
+                tv[h] = s;
+                slot_keys[s] = (i64)k;
+                slot = s;
+                is_new = 1;
+                break;
+            }
+            if (prev == k) { slot = (i64)tv[h]; break; }
+        }
+        h = (h + 1) & (u64)mask;
+    }
+    return slot;
+}
+
 __global__ void k_ht_lookup(u64* __restrict__ tk, int* __restrict__ tv,
                             long mask, const i64* __restrict__ keys, long n,
                             int* __restrict__ nrows,
@@ -503,37 +542,114 @@ __global__ void k_ht_lookup(u64* __restrict__ tk, int* __restrict__ tv,
         if (new_mask) new_mask[i] = 0;
         return;
     }
-    u64 h = splitmix64(k) & (u64)mask;
-    i64 slot = -1;
-    unsigned char is_new = 0;
-    // bounded probe: a full table (host sizing bug) yields slot -1 (miss)
-    // instead of hanging the GPU
-    for (long p = 0; p <= mask; ++p) {
-        u64 cur = tk[h];
-        if (cur == k) { slot = (i64)tv[h]; break; }
-        if (cur == EMPTY) {
-            if (!insert) { slot = -1; break; }
-            u64 prev = atomicCAS(&tk[h], EMPTY, k);
-            if (prev == EMPTY) {
-                int s = atomicAdd(nrows, 1);
-                if (s >= row_cap) {  // slab full (host sizing bug or a
-                    tv[h] = -1;      // graph-captured insert): this call AND
-                    slot = -1;       // every later lookup of this key must
-                    break;           // see a miss — a never-written tv[h]
-                }                    // here would later read as a garbage
-                                     // slot index (OOB row access)
-                tv[h] = s;
-                slot_keys[s] = (i64)k;
-                slot = s;
-                is_new = 1;
-                break;
-            }
-            if (prev == k) { slot = (i64)tv[h]; break; }
-        }
-        h = (h + 1) & (u64)mask;
-    }
+    unsigned char is_new;
+    i64 slot = ht_probe(tk, tv, mask, k, insert, nrows, slot_keys, row_cap,
+                        is_new);
     slots[i] = slot;
     if (new_mask) new_mask[i] = is_new;
+}
+
+// ------------------------------------------------------ feature admission
+// A count-min filter in front of the insert: a key that misses the table
+// earns a row only once it was seen min_count times. sketch is D rows of W
+// int32 counters (W a power of two); the cell of key k in row j is
+// j*W + (splitmix64(splitmix64(k) ^ (seed + j)) & (W-1)), the same function
+// as ops/dispatch.py admit_cells.
+//
+// Two launches. k_admit_note probes read-only; a miss adds 1 to its D cells
+// and leaves the marker ADMIT_PENDING. k_admit_resolve, after the kernel
+// boundary, reads the D cells back with plain loads: every add of the call
+// has landed, so the estimate of a key that shares a cell with another key
+// of the same call does not depend on which thread ran first. One kernel
+// could not give that. The adds are one dword per lane at hashed addresses,
+// the slow shape for atomics; that is the sketch's nature, and a call has
+// only D of them per missing key.
+
+static constexpr i64 ADMIT_PENDING = -2;
+
+DEV long admit_cell(u64 hk, u64 seed, int j, long W) {
+    return (long)j * W + (long)(splitmix64(hk ^ (seed + (u64)j))
+                                & (u64)(W - 1));
+}
+
+__global__ void k_admit_note(const u64* __restrict__ tk,
+                             const int* __restrict__ tv, long mask,
+                             const i64* __restrict__ keys, long n,
+                             int* __restrict__ sketch, long W, int D,
+                             u64 seed, i64* __restrict__ slots,
+                             unsigned char* __restrict__ new_mask,
+                             const int* __restrict__ u_dev) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    new_mask[i] = 0;
+    if (u_dev && i >= *u_dev) { slots[i] = -1; return; }  // as k_ht_lookup
+    u64 k = (u64)keys[i];
+    if (k == EMPTY) { slots[i] = -1; return; }            // reserved key
+    u64 h = splitmix64(k) & (u64)mask;
+    for (long p = 0; p <= mask; ++p) {
+        u64 cur = tk[h];
+        if (cur == k) { slots[i] = (i64)tv[h]; return; }
+        if (cur == EMPTY) break;
+        h = (h + 1) & (u64)mask;
+    }
+    u64 hk = splitmix64(k);
+    for (int j = 0; j < D; ++j)
+        atomicAdd(&sketch[admit_cell(hk, seed, j, W)], 1);  // no return used
+    slots[i] = ADMIT_PENDING;
+}
+
+// stats[0] admitted, stats[1] turned away (a sighting that got no row, the
+// slab-full case included): one atomic per wave and counter
+__global__ void k_admit_resolve(u64* __restrict__ tk, int* __restrict__ tv,
+                                long mask, const i64* __restrict__ keys,
+                                long n, const int* __restrict__ sketch,
+                                long W, int D, u64 seed, int min_count,
+                                int* __restrict__ nrows,
+                                i64* __restrict__ slot_keys, long row_cap,
+                                i64* __restrict__ slots,
+                                unsigned char* __restrict__ new_mask,
+                                u64* __restrict__ stats) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool pending = i < n && slots[i] == ADMIT_PENDING;
+    bool admitted = false;
+    if (pending) {
+        u64 k = (u64)keys[i];
+        u64 hk = splitmix64(k);
+        int est = sketch[admit_cell(hk, seed, 0, W)];
+        for (int j = 1; j < D; ++j) {
+            int c = sketch[admit_cell(hk, seed, j, W)];
+            est = c < est ? c : est;
+        }
+        i64 slot = -1;
+        unsigned char is_new = 0;
+        if (est >= min_count)
+            slot = ht_probe(tk, tv, mask, k, 1, nrows, slot_keys, row_cap,
+                            is_new);
+        slots[i] = slot;
+        new_mask[i] = is_new;
+        admitted = slot >= 0;
+    }
+    u64 adm = __ballot(admitted);
+    u64 away = __ballot(pending && !admitted);
+    if ((threadIdx.x & 63) == 0) {
+        if (adm) atomicAdd(&stats[0], (u64)__popcll(adm));
+        if (away) atomicAdd(&stats[1], (u64)__popcll(away));
+    }
+}
+
+// ageing: every counter >> shift (arithmetic; shift >= 31 zeroes), four
+// counters per thread through 16-byte loads and stores, scalar tail
+__global__ void k_admit_age(int* __restrict__ sketch, long n, int shift) {
+    long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long n4 = n >> 2;
+    if (q < n4) {
+        int4 v = reinterpret_cast<int4*>(sketch)[q];
+        if (shift >= 31) v = make_int4(0, 0, 0, 0);
+        else { v.x >>= shift; v.y >>= shift; v.z >>= shift; v.w >>= shift; }
+        reinterpret_cast<int4*>(sketch)[q] = v;
+    }
+    long t = (n4 << 2) + q;
+    if (q < 3 && t < n) sketch[t] = shift >= 31 ? 0 : sketch[t] >> shift;
 }
 
 __global__ void k_ht_rehash(const u64* __restrict__ tk_old,
@@ -3229,6 +3345,26 @@ void emb_ht_lookup(u64* tk, int* tv, long cap, const i64* keys, long n,
                                                  nrows, slot_keys, slots,
                                                  new_mask, insert, u_dev,
                                                  row_cap);
+}
+
+// slots doubles as the hand-over between the two launches (ADMIT_PENDING)
+void emb_ht_lookup_admit(u64* tk, int* tv, long cap, const i64* keys, long n,
+                         int* nrows, i64* slot_keys, long row_cap,
+                         int* sketch, long W, int D, u64 seed, int min_count,
+                         u64* stats, i64* slots, unsigned char* new_mask,
+                         const int* u_dev, hipStream_t stream) {
+    k_admit_note<<<grid1d(n), BLOCK, 0, stream>>>(tk, tv, cap - 1, keys, n,
+                                                  sketch, W, D, seed, slots,
+                                                  new_mask, u_dev);
+    k_admit_resolve<<<grid1d(n), BLOCK, 0, stream>>>(
+        tk, tv, cap - 1, keys, n, sketch, W, D, seed, min_count, nrows,
+        slot_keys, row_cap, slots, new_mask, stats);
+}
+
+void emb_admit_age(int* sketch, long n, int shift, hipStream_t stream) {
+    // one thread per four counters; the first three also take the tail
+    int grid = grid1d((n >> 2) > 3 ? (n >> 2) : 3);
+    if (n) k_admit_age<<<grid, BLOCK, 0, stream>>>(sketch, n, shift);
 }
 
 void emb_ht_rehash(const u64* tk_old, const int* tv_old, long cap_old,

@@ -126,6 +126,54 @@ def reduce_apply_by_index(opt_id: int, weights: torch.Tensor,
                         list(cfg), u_dev)
 
 
+# ---------------------------------------------------------- feature admission
+# The count-min filter in front of a hashed row's creation. ``sketch`` is one
+# flat int32 tensor of ``depth`` rows of ``width`` counters, width a power of
+# two. The torch forms are the CPU path and the oracle of k_admit_note /
+# k_admit_resolve / k_admit_age (ops/csrc/embops.hip).
+
+def admit_cells(keys: torch.Tensor, width: int, depth: int, seed: int
+                ) -> torch.Tensor:
+    """The sketch cells of ``keys`` (int64 [n]) -> int64 [depth, n]: row j
+    holds ``j*width + (splitmix64(splitmix64(k) ^ (seed + j)) & (width-1))``
+    in wrap-around int64 arithmetic."""
+    from ..core.rng import splitmix64
+    hk = splitmix64(keys.to(torch.int64))
+    rows = []
+    for j in range(depth):
+        sj = ((int(seed) + j + (1 << 63)) % (1 << 64)) - (1 << 63)
+        rows.append(j * width + (splitmix64(hk ^ sj) & (width - 1)))
+    return torch.stack(rows) if rows else hk.new_empty((0, keys.numel()))
+
+
+def admit_note(sketch: torch.Tensor, keys: torch.Tensor, depth: int,
+               seed: int) -> torch.Tensor:
+    """One sighting of each of ``keys`` (unique int64 [n], all missing from
+    the table): add 1 to every key's cells, then return the estimates
+    (int32 [n]), each the minimum of the key's cells AFTER all adds."""
+    cells = admit_cells(keys, sketch.numel() // depth, depth, seed)
+    sketch.index_add_(0, cells.reshape(-1),
+                      torch.ones(cells.numel(), dtype=sketch.dtype,
+                                 device=sketch.device))
+    return sketch[cells].min(dim=0).values
+
+
+def admit_age(sketch: torch.Tensor, shift: int) -> None:
+    """Every counter ``>> shift`` in place; ``shift >= 31`` zeroes."""
+    shift = int(shift)
+    if shift < 0:
+        raise ValueError("shift must not be negative")
+    if _use_hip(sketch):
+        ext = require_hip()
+        if ext is not None:
+            ext.admit_age(sketch, shift)
+            return
+    if shift >= 31:
+        sketch.zero_()
+    else:
+        sketch.copy_(sketch >> shift)
+
+
 # ------------------------------------------------------------ multi-hot bags
 
 POOL_MODES = {"sum": 0, "mean": 1, "sqrtn": 2}

@@ -170,6 +170,19 @@ class ShardedVariable:
     def set_optimizer(self, category: str, **cfg):
         self.shard.set_optimizer(category, **cfg)
 
+    def set_admission(self, min_count, **cfg):
+        """Admission filter of the local shard (hash mode):
+        ``VariableShard.set_admission``. Every rank sets the same values;
+        each shard counts the sightings of the keys it owns."""
+        self.shard.set_admission(min_count, **cfg)
+
+    def age_admission(self, shift: int = 1) -> None:
+        self.shard.age_admission(shift)
+
+    def admission_stats(self) -> dict:
+        """The local shard's ``admission_stats()``."""
+        return self.shard.admission_stats()
+
     def reserve_rows(self, total_rows: int) -> None:
         """Pre-size this shard for its share of ``total_rows`` keys (hash
         mode; makes the GPU insert path hipGraph-capturable)."""

@@ -793,6 +793,18 @@ def make_app(controller: Optional[ModelController] = None,
                          f' {a.n}')
             lines.append(f'openembedding_metric{{name="{safe}",stat="sum"}}'
                          f' {a.total}')
+        # admission filters of a trainer living in this process (a served
+        # table is read-only and has none): sightings that got a row and
+        # sightings that were turned away, per variable
+        from . import context as _ctxmod
+        tctx = _ctxmod._context
+        for vid, v in sorted(tctx.variables.items()) if tctx else ():
+            if getattr(v.shard, "_admit", None) is None:
+                continue
+            st = v.shard.admission_stats()
+            for stat in ("admitted", "turned_away"):
+                lines.append(f'openembedding_admission{{variable="{vid}",'
+                             f'stat="{stat}"}} {st[stat]}')
         lines.append(f'openembedding_models {len(controller.manager.signs())}')
         return PlainTextResponse("\n".join(lines) + "\n")
 

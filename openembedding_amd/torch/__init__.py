@@ -38,6 +38,7 @@ __all__ = [
     "Model", "save_server_model", "load_server_model",
     "track_server_model_changes", "save_server_model_delta",
     "load_server_model_delta", "expire_server_model",
+    "age_admission_filters", "admission_stats",
     "save_as_original_model", "pulling", "sparse_read_as_dense",
     "should_persist_server_model", "persist_server_model",
     "restore_server_model", "get_context",
@@ -173,10 +174,16 @@ class Embedding(nn.Module):
     ``sparse_as_dense``: keep this table as an ordinary replicated
     nn.Embedding trained by allreduce — the reference's "cache" policy for
     small hot vocabularies (exb.py:241-248, ~+10%: documents/en/benchmark.md).
+
+    ``admission`` (hash mode only), for example ``{"min_count": 3}``: an id
+    earns its row only after it was seen in that many training steps; until
+    then it reads as a zero row and its gradient is dropped. The keywords
+    are ``VariableShard.set_admission``'s (min_count, width, depth, seed).
     """
 
     def __init__(self, num_embeddings: int, embedding_dim: int,
                  initializer: Optional[Dict] = None,
+                 admission: Optional[Dict] = None,
                  num_shards: Optional[int] = None,
                  sparse_as_dense: bool = False,
                  storage: Optional[Storage] = None,
@@ -207,6 +214,8 @@ class Embedding(nn.Module):
                                    "maxval": 1.0 / max(1, int(math.sqrt(embedding_dim)))}
             cat = init.pop("category") if "category" in init else "uniform"
             sharded.set_initializer(cat, **init)
+            if admission:
+                sharded.set_admission(**admission)
             self.variable = Variable(sharded, st)
             # zero-size hook so autograd reaches our Function even though
             # indices carry no grad
@@ -1013,6 +1022,24 @@ def expire_server_model(max_age: Optional[int] = None,
                 "them (forward, backward, step) first")
     from ..checkpoint import expire_rows
     return expire_rows(get_context(), max_age=max_age, before=before)
+
+
+def age_admission_filters(shift: int = 1) -> None:
+    """Halve (``>> shift``) every counter of every variable's admission
+    filter; ``shift >= 31`` empties them. A sketch on an endless stream
+    fills up and then admits everything, so call this at a fixed cadence
+    (a save interval, say). Every rank calls it."""
+    for v in get_context().variables.values():
+        if getattr(v.shard, "_admit", None) is not None:
+            v.shard.age_admission(shift)
+
+
+def admission_stats() -> Dict[int, dict]:
+    """variable id -> the local shard's ``admission_stats()``, for the
+    variables whose admission filter is on."""
+    return {vid: v.shard.admission_stats()
+            for vid, v in get_context().variables.items()
+            if getattr(v.shard, "_admit", None) is not None}
 
 
 def save_as_original_model(model: nn.Module, path: str,
