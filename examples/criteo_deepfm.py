@@ -30,7 +30,7 @@ from openembedding_amd.models import MODELS, synthetic_batch
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--model", default="deepfm",
-                   choices=["deepfm", "wdl", "xdeepfm", "lr"])
+                   choices=["deepfm", "wdl", "xdeepfm", "lr", "dlrm"])
     p.add_argument("--dim", type=int, default=9)
     p.add_argument("--batch", type=int, default=4096)
     p.add_argument("--steps", type=int, default=100)

@@ -311,6 +311,9 @@ def build_graph(model) -> GraphBuilder:
     """TF graph for one model of the zoo, mirroring models/ctr.py math."""
     from .models import ctr
 
+    if not isinstance(model, ctr._CTRBase):
+        # e.g. DLRM: no first-order column, no dense_linear to mirror
+        raise NotImplementedError(type(model).__name__)
     g = GraphBuilder()
     e, lin, _ = _common_inputs(g, model)
     logits = _first_order(g, model, lin)

@@ -1,9 +1,10 @@
-"""CTR model zoo: LR, WDL, DeepFM, xDeepFM.
+"""CTR model zoo: LR, WDL, DeepFM, xDeepFM, DLRM.
 
-The reference trains these via DeepCTR/Keras (examples/criteo_deepctr_*.py,
-test/benchmark/criteo_deepctr.py); here they are native torch modules whose
-sparse features go through the PS-backed CombinedEmbedding (one fused pull
-per step for all 26 fields — see openembedding_amd/torch/__init__.py).
+The reference trains the first four via DeepCTR/Keras
+(examples/criteo_deepctr_*.py, test/benchmark/criteo_deepctr.py); here they
+are native torch modules whose sparse features go through the PS-backed
+CombinedEmbedding (one fused pull per step for all 26 fields — see
+openembedding_amd/torch/__init__.py).
 
 All models take (dense [B,13] float32, sparse [B,26] int64 per-field ids)
 and return logits [B].
@@ -19,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from ..ops import hip_available
+from ..ops.dispatch import dot_interact
 from ..torch import CombinedEmbedding
 from .criteo import CRITEO_FIELD_VOCABS, N_DENSE
 
@@ -253,55 +255,20 @@ def _mlp(in_dim: int, hidden: Sequence[int], out_dim: int = 1) -> nn.Sequential:
     return nn.Sequential(*layers)
 
 
-class _CTRBase(nn.Module):
-    """Shared CTR skeleton.
+class _DNNHead(nn.Module):
+    """What every model with a ``dnn`` tower shares: the switches that
+    ``convert_mlp_bf16`` sets and the tower's forward."""
 
-    MI355X-first layout: the per-key first-order ("linear"/wide) weight is
-    stored as an EXTRA COLUMN of the same PS variable (rows are dim+1 wide)
-    instead of the reference's separate dim-1 Embedding — one fused
-    unique/all_to_all/gather per step instead of two, with identical
-    per-element optimizer math (all sparse optimizers are element-wise; the
-    per-row scalar states advance on the same touch pattern either way)."""
-
-    def __init__(self, field_vocabs: Optional[List[int]], dim: int,
-                 sparse_as_dense_size: int = 0, hash_mode: bool = False):
+    def __init__(self):
         super().__init__()
-        self.field_vocabs = list(field_vocabs or CRITEO_FIELD_VOCABS)
-        self.dim = dim
-        self.n_fields = len(self.field_vocabs)
-        self.embedding = CombinedEmbedding(self.field_vocabs, dim + 1,
-                                           hash_mode=hash_mode)
-        self.dense_linear = nn.Linear(N_DENSE, 1)
-        # fused interaction head on GPU (ctrhead.hip); deep_in dtype follows
-        # head_bf16 (fp32 measured faster than bf16 autocast on MI355X for
-        # these skinny GEMMs — gpurun_out/bench_fp32graph.log)
+        # fused interaction head on GPU (ctrhead.hip, dlrm.hip); deep_in
+        # dtype follows head_bf16 (fp32 measured faster than bf16 autocast
+        # on MI355X for these skinny GEMMs)
         self.head_bf16 = False
         # whole-MLP fused kernel (mlp.hip): enabled by convert_mlp_bf16 when
-        # the dnn matches Linear/ReLU x3 + Linear(H,1), H <= 512 (% 16)
+        # the dnn matches Linear/ReLU x3 + Linear(H,1), H <= 416 (% 16)
         self.fused_mlp = False
         self._w1pad = None
-
-    def _embed(self, sparse: torch.Tensor):
-        """-> (e [B,F,dim], linear_w [B,F])."""
-        e_all = self.embedding(sparse)
-        return e_all[..., :self.dim], e_all[..., self.dim]
-
-    def _first_order(self, dense: torch.Tensor, linear_w: torch.Tensor
-                     ) -> torch.Tensor:
-        return linear_w.sum(dim=1) + self.dense_linear(dense).squeeze(-1)
-
-    def _use_fused_head(self, t: torch.Tensor) -> bool:
-        # kernel limit: each wave lane covers <=2 row columns -> dim+1 <= 128
-        return (t.is_cuda and 1 <= self.dim + 1 <= 128 and hip_available())
-
-    def _fused_head(self, dense: torch.Tensor, sparse: torch.Tensor,
-                    use_fm: bool):
-        """-> (e_all [B,F,dim+1], deep_in [B,F*dim+ND(+pad)], partial [B])."""
-        e_all = self.embedding(sparse)
-        deep_in, partial = _FusedCTRHeadFn.apply(
-            e_all, dense, self.dense_linear.weight, self.dense_linear.bias,
-            use_fm, self.head_bf16, self.fused_mlp)
-        return e_all, deep_in, partial
 
     def _dnn_out(self, deep_in: torch.Tensor,
                  partial: torch.Tensor = None) -> torch.Tensor:
@@ -326,6 +293,49 @@ class _CTRBase(nn.Module):
         w_dtype = next(self.dnn.parameters()).dtype
         out = self.dnn(deep_in.to(w_dtype)).squeeze(-1).float()
         return out if partial is None else partial + out
+
+
+class _CTRBase(_DNNHead):
+    """Shared CTR skeleton.
+
+    MI355X-first layout: the per-key first-order ("linear"/wide) weight is
+    stored as an EXTRA COLUMN of the same PS variable (rows are dim+1 wide)
+    instead of the reference's separate dim-1 Embedding — one fused
+    unique/all_to_all/gather per step instead of two, with identical
+    per-element optimizer math (all sparse optimizers are element-wise; the
+    per-row scalar states advance on the same touch pattern either way)."""
+
+    def __init__(self, field_vocabs: Optional[List[int]], dim: int,
+                 sparse_as_dense_size: int = 0, hash_mode: bool = False):
+        super().__init__()
+        self.field_vocabs = list(field_vocabs or CRITEO_FIELD_VOCABS)
+        self.dim = dim
+        self.n_fields = len(self.field_vocabs)
+        self.embedding = CombinedEmbedding(self.field_vocabs, dim + 1,
+                                           hash_mode=hash_mode)
+        self.dense_linear = nn.Linear(N_DENSE, 1)
+
+    def _embed(self, sparse: torch.Tensor):
+        """-> (e [B,F,dim], linear_w [B,F])."""
+        e_all = self.embedding(sparse)
+        return e_all[..., :self.dim], e_all[..., self.dim]
+
+    def _first_order(self, dense: torch.Tensor, linear_w: torch.Tensor
+                     ) -> torch.Tensor:
+        return linear_w.sum(dim=1) + self.dense_linear(dense).squeeze(-1)
+
+    def _use_fused_head(self, t: torch.Tensor) -> bool:
+        # kernel limit: each wave lane covers <=2 row columns -> dim+1 <= 128
+        return (t.is_cuda and 1 <= self.dim + 1 <= 128 and hip_available())
+
+    def _fused_head(self, dense: torch.Tensor, sparse: torch.Tensor,
+                    use_fm: bool):
+        """-> (e_all [B,F,dim+1], deep_in [B,F*dim+ND(+pad)], partial [B])."""
+        e_all = self.embedding(sparse)
+        deep_in, partial = _FusedCTRHeadFn.apply(
+            e_all, dense, self.dense_linear.weight, self.dense_linear.bias,
+            use_fm, self.head_bf16, self.fused_mlp)
+        return e_all, deep_in, partial
 
 
 class LR(_CTRBase):
@@ -556,7 +566,45 @@ class xDeepFM(_CTRBase):
                 + self._dnn_out(deep_in))
 
 
-def convert_mlp_bf16(model: _CTRBase) -> _CTRBase:
+class DLRM(_DNNHead):
+    """DLRM (Naumov et al. 2019): bottom MLP over the dense features, one
+    embedding row per sparse field, pairwise dot interaction, top MLP.
+
+    No first-order column and no dense linear term: the embedding rows are
+    ``dim`` wide. The interaction — [x | strictly lower triangle of the
+    Gram matrix of (x, e_1 .. e_F)] — is ``ops.dot_interact``: one HIP
+    launch each way on the GPU (ops/csrc/dlrm.hip, F <= 31, dim <= 128).
+    After ``convert_mlp_bf16`` the kernel emits the 32-padded bf16 row that
+    the fused top MLP consumes; the bottom MLP stays plain fp32 layers."""
+
+    def __init__(self, field_vocabs: Optional[List[int]] = None,
+                 dim: int = 16, bottom: Sequence[int] = (512, 256),
+                 hidden: Sequence[int] = (400, 400, 400),
+                 hash_mode: bool = False):
+        super().__init__()
+        self.field_vocabs = list(field_vocabs or CRITEO_FIELD_VOCABS)
+        self.dim = dim
+        self.n_fields = len(self.field_vocabs)
+        self.embedding = CombinedEmbedding(self.field_vocabs, dim,
+                                           hash_mode=hash_mode)
+        layers: List[nn.Module] = []
+        d = N_DENSE
+        for h in list(bottom) + [dim]:
+            layers += [nn.Linear(d, h), nn.ReLU()]
+            d = h
+        self.bottom_mlp = nn.Sequential(*layers)
+        t = self.n_fields + 1
+        self.dnn = _mlp(dim + t * (t - 1) // 2, hidden)
+
+    def forward(self, dense: torch.Tensor, sparse: torch.Tensor) -> torch.Tensor:
+        x = self.bottom_mlp(dense)                       # [B, dim]
+        e = self.embedding(sparse)                       # [B, F, dim]
+        fused = self.fused_mlp and self.head_bf16 and x.is_cuda
+        deep_in = dot_interact(e, x, out_bf16=fused, pad32=fused)
+        return self._dnn_out(deep_in)
+
+
+def convert_mlp_bf16(model: _DNNHead) -> _DNNHead:
     """Native-bf16 MLP: the dnn's weights LIVE in bf16 (straight into MFMA
     GEMMs, no per-step autocast casts; the flat optimizer keeps an fp32
     master) and the fused head emits bf16 deep_in. dense_linear stays fp32
@@ -581,4 +629,5 @@ def convert_mlp_bf16(model: _CTRBase) -> _CTRBase:
     return model
 
 
-MODELS = {"lr": LR, "wdl": WDL, "deepfm": DeepFM, "xdeepfm": xDeepFM}
+MODELS = {"lr": LR, "wdl": WDL, "deepfm": DeepFM, "xdeepfm": xDeepFM,
+          "dlrm": DLRM}

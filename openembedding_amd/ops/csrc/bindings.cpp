@@ -114,6 +114,13 @@ void emb_ctr_head_bwd_rows(const float*, const float*, const float*,
                            const void*, const float*, const float*, long,
                            long, long, long, long, float*, float*, float*,
                            float*, int, int, int, hipStream_t_);
+long emb_dot_interact_width(long, long, int);
+int emb_dot_interact_waves(long, long, long, long, long, int);
+void emb_dot_interact_fwd(const float*, const float*, void*, long, long,
+                          long, long, int, int, hipStream_t_);
+void emb_dot_interact_bwd(const float*, const float*, const void*, float*,
+                          float*, long, long, long, long, int, int,
+                          hipStream_t_);
 void emb_mlp3_bias_bwd(const float*, const void*, const void*, const void*,
                        const void*, long, long, float*, void*, void*, void*,
                        void*, void*, int, int, hipStream_t_);
@@ -2017,6 +2024,72 @@ void mlp3_bias_bwd(torch::Tensor dout, torch::Tensor dz1, torch::Tensor dz2,
                       with_head ? 1 : 0, cur_stream());
 }
 
+// ---- DLRM pairwise dot interaction (dlrm.hip) ---------------------------
+
+// Everything the kernels rely on, checked before a launch; returns the row
+// stride of out / d_out. The Python side (ops.dot_interact) routes what is
+// refused here to torch.
+static long dot_interact_check(const torch::Tensor& e,
+                               const torch::Tensor& x, bool pad32,
+                               const char* who) {
+    TORCH_CHECK(e.is_cuda() && x.is_cuda() && e.device() == x.device(), who,
+                ": e and x must be on one GPU");
+    TORCH_CHECK(e.scalar_type() == torch::kFloat32
+                && x.scalar_type() == torch::kFloat32, who,
+                ": e and x must be float32");
+    TORCH_CHECK(e.dim() == 3 && x.dim() == 2 && x.size(0) == e.size(0)
+                && x.size(1) == e.size(2), who,
+                ": e must be [B, F, D] and x [B, D]");
+    TORCH_CHECK(e.is_contiguous() && x.is_contiguous(), who,
+                ": e and x must be contiguous");
+    const long B = e.size(0), F = e.size(1), D = e.size(2);
+    TORCH_CHECK(F >= 1 && F <= 31, who, ": F must be in 1..31");
+    TORCH_CHECK(D >= 1 && D <= 128, who, ": D must be in 1..128");
+    const long W = emb_dot_interact_width(F, D, pad32 ? 1 : 0);
+    TORCH_CHECK(B * F * D < (1L << 31) && B * W < (1L << 31), who,
+                ": B*F*D and B*Kp must fit int32");
+    return W;
+}
+
+torch::Tensor dot_interact_fwd(torch::Tensor e, torch::Tensor x,
+                               bool out_bf16, bool pad32) {
+    const long W = dot_interact_check(e, x, pad32, "dot_interact_fwd");
+    const c10::cuda::CUDAGuard guard(e.device());
+    const long B = e.size(0), F = e.size(1), D = e.size(2);
+    const long esz = out_bf16 ? 2 : 4;
+    const int S = emb_dot_interact_waves(B, F, D, W, esz, 0);
+    TORCH_CHECK(S > 0, "dot_interact_fwd: shape does not fit the kernel");
+    auto out = torch::empty({B, W}, e.options().dtype(
+        out_bf16 ? torch::kBFloat16 : torch::kFloat32));
+    emb_dot_interact_fwd(e.data_ptr<float>(), x.data_ptr<float>(),
+                         out.data_ptr(), B, F, D, W, out_bf16 ? 1 : 0, S,
+                         cur_stream());
+    return out;
+}
+
+std::tuple<torch::Tensor, torch::Tensor> dot_interact_bwd(
+    torch::Tensor e, torch::Tensor x, torch::Tensor d_out, bool pad32) {
+    const long W = dot_interact_check(e, x, pad32, "dot_interact_bwd");
+    const long B = e.size(0), F = e.size(1), D = e.size(2);
+    const bool g_bf16 = d_out.scalar_type() == torch::kBFloat16;
+    TORCH_CHECK(d_out.is_cuda() && d_out.device() == e.device()
+                && (g_bf16 || d_out.scalar_type() == torch::kFloat32)
+                && d_out.dim() == 2 && d_out.size(0) == B
+                && d_out.size(1) == W && d_out.is_contiguous(),
+                "dot_interact_bwd: d_out must be a contiguous bf16 or fp32 "
+                "[B, ", W, "] on e's device");
+    const c10::cuda::CUDAGuard guard(e.device());
+    const int S = emb_dot_interact_waves(B, F, D, W, g_bf16 ? 2 : 4, 1);
+    TORCH_CHECK(S > 0, "dot_interact_bwd: shape does not fit the kernel");
+    auto de = torch::empty_like(e);
+    auto dx = torch::empty_like(x);
+    emb_dot_interact_bwd(e.data_ptr<float>(), x.data_ptr<float>(),
+                         d_out.data_ptr(), de.data_ptr<float>(),
+                         dx.data_ptr<float>(), B, F, D, W, g_bf16 ? 1 : 0, S,
+                         cur_stream());
+    return {de, dx};
+}
+
 // ---- CIN implicit-GEMM -------------------------------------------------
 
 torch::Tensor cin_fwd(torch::Tensor x0p, torch::Tensor xkp,
@@ -2554,6 +2627,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("db2"), pybind11::arg("db3"), pybind11::arg("dw4"),
           pybind11::arg("db4"), pybind11::arg("with_dz") = true,
           pybind11::arg("with_head") = true);
+    m.def("dot_interact_fwd", &dot_interact_fwd,
+          "DLRM interaction fwd: [x | strict lower triangle of the Gram "
+          "matrix of (x, e rows)] on MFMA, one launch",
+          pybind11::arg("e"), pybind11::arg("x"), pybind11::arg("out_bf16"),
+          pybind11::arg("pad32"));
+    m.def("dot_interact_bwd", &dot_interact_bwd,
+          "DLRM interaction bwd: (de, dx) from d_out, one launch, no atomics",
+          pybind11::arg("e"), pybind11::arg("x"), pybind11::arg("d_out"),
+          pybind11::arg("pad32"));
     m.def("cin_fwd", &cin_fwd,
           "CIN layer forward: implicit outer-product MFMA GEMM");
     m.def("cin_dw", &cin_dw,

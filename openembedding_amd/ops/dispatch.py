@@ -7,6 +7,7 @@ are tested against the torch versions in tests/test_gpu_numerics.py.
 
 from __future__ import annotations
 
+import os
 from typing import Tuple
 
 import torch
@@ -548,6 +549,96 @@ def dequantize_rows(packed: torch.Tensor, dim: int, fmt: str) -> torch.Tensor:
     scale = packed[:, cw:cw + 4].contiguous().view(torch.float32).view(n, 1)
     lo = packed[:, cw + 4:].contiguous().view(torch.float32).view(n, 1)
     return lo + scale * packed[:, :dim].float()
+
+
+# ------------------------------------------------- DLRM dot interaction
+# out[b] = [x[b] | <v_i, v_j> for 0 <= j < i < T (tril_indices order) | pad]
+# with v_0 = x[b], v_1.. = e[b]; x and e rounded to bf16 once as operands
+# of the dots, fp32 sums. ops/csrc/dlrm.hip does it in one launch each way;
+# OEAMD_DLRM_DOT=0 keeps the torch route on the GPU in the same build (A/B
+# runs). Read once at import.
+_DLRM_DOT = os.environ.get("OEAMD_DLRM_DOT", "1") != "0"
+
+
+class _RoundGradBF16Fn(torch.autograd.Function):
+    """Identity whose gradient is rounded to bf16 once (what d_out is when
+    it comes out of the fused MLP backward)."""
+
+    @staticmethod
+    def forward(ctx, t):
+        return t.view_as(t)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(torch.bfloat16).to(g.dtype)
+
+
+def _dot_interact_torch(e: torch.Tensor, x: torch.Tensor, out_bf16: bool,
+                        pad32: bool) -> torch.Tensor:
+    B, F, D = e.shape
+    T = F + 1
+    v = torch.cat([x.unsqueeze(1), e], dim=1)
+    # straight-through rounding: v + (r - v) is r exactly, and the gradient
+    # passes unrounded
+    vr = (v + (v.to(torch.bfloat16).to(v.dtype) - v).detach()).float()
+    gram = torch.bmm(vr, vr.transpose(1, 2))
+    li, lj = torch.tril_indices(T, T, -1, device=e.device)
+    out = torch.cat([x.float(), gram[:, li, lj]], dim=1)
+    out = _RoundGradBF16Fn.apply(out)
+    if out_bf16:
+        out = out.to(torch.bfloat16)
+    if pad32:
+        out = torch.nn.functional.pad(out, (0, -out.shape[1] % 32))
+    return out
+
+
+class _DotInteractFn(torch.autograd.Function):
+    """k_dot_interact_fwd / k_dot_interact_bwd. Nothing extra is saved: the
+    backward recomputes the bf16 operands from e and x."""
+
+    @staticmethod
+    def forward(ctx, e, x, out_bf16, pad32):
+        ctx.save_for_backward(e, x)
+        ctx.pad32 = pad32
+        return require_hip().dot_interact_fwd(e, x, out_bf16, pad32)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        e, x = ctx.saved_tensors
+        de, dx = require_hip().dot_interact_bwd(e, x, d_out.contiguous(),
+                                                ctx.pad32)
+        return de, dx, None, None
+
+
+def _dot_interact_fits(e: torch.Tensor, x: torch.Tensor) -> bool:
+    """The limits the binding checks (it refuses everything else)."""
+    if not (_use_hip(e) and x.device == e.device and e.dim() == 3
+            and x.dim() == 2 and e.dtype == x.dtype == torch.float32
+            and e.is_contiguous() and x.is_contiguous()):
+        return False
+    B, F, D = e.shape
+    Kp = (D + F * (F + 1) // 2 + 31) // 32 * 32
+    return (1 <= F <= 31 and 1 <= D <= 128 and B * F * D < 2 ** 31
+            and B * Kp < 2 ** 31)
+
+
+def dot_interact(e: torch.Tensor, x: torch.Tensor, out_bf16: bool = False,
+                 pad32: bool = False) -> torch.Tensor:
+    """DLRM's pairwise dot interaction, differentiable w.r.t. e and x.
+
+    e [B, F, D] embedding rows, x [B, D] bottom-MLP output ->
+    [B, D + T(T-1)/2] (T = F + 1; 32-padded with zeros when ``pad32``),
+    bf16 when ``out_bf16`` else fp32: x in front (unrounded), then the
+    strictly lower triangle of the Gram matrix of (x, e_1 .. e_F) in
+    ``torch.tril_indices(T, T, -1)`` order. x and e enter the dots rounded
+    to bf16, the sums are fp32; the gradient coming in is rounded to bf16
+    once. GPU: one HIP launch each way for contiguous fp32 operands with
+    F <= 31 and D <= 128; everything else, and the CPU, takes torch ops."""
+    if e.dim() != 3 or x.dim() != 2 or x.shape != (e.shape[0], e.shape[2]):
+        raise ValueError("dot_interact takes e [B, F, D] and x [B, D]")
+    if _DLRM_DOT and _dot_interact_fits(e, x) and require_hip() is not None:
+        return _DotInteractFn.apply(e, x, out_bf16, pad32)
+    return _dot_interact_torch(e, x, out_bf16, pad32)
 
 
 # ----------------------------------------------------------------- fused loss

@@ -23,6 +23,7 @@ ext = CUDAExtension(
         "openembedding_amd/ops/csrc/ctrhead.hip",
         "openembedding_amd/ops/csrc/mlp.hip",
         "openembedding_amd/ops/csrc/cin.hip",
+        "openembedding_amd/ops/csrc/dlrm.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3"],
