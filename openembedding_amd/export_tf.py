@@ -314,6 +314,9 @@ def build_graph(model) -> GraphBuilder:
     if not isinstance(model, ctr._CTRBase):
         # e.g. DLRM: no first-order column, no dense_linear to mirror
         raise NotImplementedError(type(model).__name__)
+    if isinstance(model, ctr.DCN):
+        # the interpreter's graph has no cross layer to mirror
+        raise NotImplementedError("DCN")
     g = GraphBuilder()
     e, lin, _ = _common_inputs(g, model)
     logits = _first_order(g, model, lin)

@@ -1,5 +1,5 @@
 from .criteo import CRITEO_FIELD_VOCABS, N_DENSE, N_SPARSE, synthetic_batch
-from .ctr import CIN, DLRM, LR, MODELS, WDL, DeepFM, xDeepFM
+from .ctr import CIN, DCN, DLRM, LR, MODELS, WDL, DeepFM, xDeepFM
 
 __all__ = ["CRITEO_FIELD_VOCABS", "N_DENSE", "N_SPARSE", "synthetic_batch",
-           "CIN", "DLRM", "LR", "MODELS", "WDL", "DeepFM", "xDeepFM"]
+           "CIN", "DCN", "DLRM", "LR", "MODELS", "WDL", "DeepFM", "xDeepFM"]

@@ -1,4 +1,4 @@
-"""CTR model zoo: LR, WDL, DeepFM, xDeepFM, DLRM.
+"""CTR model zoo: LR, WDL, DeepFM, xDeepFM, DLRM, DCN.
 
 The reference trains the first four via DeepCTR/Keras
 (examples/criteo_deepctr_*.py, test/benchmark/criteo_deepctr.py); here they
@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from ..ops import hip_available
-from ..ops.dispatch import dot_interact
+from ..ops.dispatch import cross_network, dot_interact
 from ..torch import CombinedEmbedding
 from .criteo import CRITEO_FIELD_VOCABS, N_DENSE
 
@@ -268,6 +268,9 @@ class _DNNHead(nn.Module):
         # whole-MLP fused kernel (mlp.hip): enabled by convert_mlp_bf16 when
         # the dnn matches Linear/ReLU x3 + Linear(H,1), H <= 416 (% 16)
         self.fused_mlp = False
+        # fused cross network (cross.hip): enabled by convert_mlp_bf16 for
+        # a DCN whose padded row is <= 512 wide with <= 6 cross layers
+        self.fused_cross = False
         self._w1pad = None
 
     def _dnn_out(self, deep_in: torch.Tensor,
@@ -334,7 +337,7 @@ class _CTRBase(_DNNHead):
         e_all = self.embedding(sparse)
         deep_in, partial = _FusedCTRHeadFn.apply(
             e_all, dense, self.dense_linear.weight, self.dense_linear.bias,
-            use_fm, self.head_bf16, self.fused_mlp)
+            use_fm, self.head_bf16, self.fused_mlp or self.fused_cross)
         return e_all, deep_in, partial
 
 
@@ -604,6 +607,58 @@ class DLRM(_DNNHead):
         return self._dnn_out(deep_in)
 
 
+class DCN(_CTRBase):
+    """DCN-v2 (Wang et al. 2021): ``cross_layers`` full-rank cross layers
+    x_{l+1} = x_0 * (W_l x_l + b_l) + x_l over the deep_in row.
+
+    ``structure="parallel"``: logit = first-order + dense-linear +
+    cross_out(x_L) + dnn(deep_in); ``"stacked"``: logit = first-order +
+    dense-linear + dnn(x_L). The cross network is ``ops.cross_network``:
+    after ``convert_mlp_bf16`` one HIP launch each way (ops/csrc/cross.hip)
+    on the head's 32-padded bf16 row - in the parallel structure with the
+    cross logit computed by the kernel and carried on as the fused MLP's
+    ``partial``, in the stacked one emitting the padded bf16 row that the
+    fused MLP consumes. Otherwise, and on the CPU, torch ops."""
+
+    def __init__(self, field_vocabs: Optional[List[int]] = None, dim: int = 9,
+                 cross_layers: int = 3,
+                 hidden: Sequence[int] = (400, 400, 400),
+                 structure: str = "parallel", **kw):
+        super().__init__(field_vocabs, dim, **kw)
+        if structure not in ("parallel", "stacked"):
+            raise ValueError("structure must be 'parallel' or 'stacked'")
+        if cross_layers < 1:
+            raise ValueError("cross_layers must be >= 1")
+        self.structure = structure
+        d = self.n_fields * dim + N_DENSE
+        self.dnn = _mlp(d, hidden)
+        self.cross_w = nn.Parameter(torch.empty(cross_layers, d, d))
+        for w in self.cross_w:
+            nn.init.xavier_uniform_(w)
+        self.cross_b = nn.Parameter(torch.zeros(cross_layers, d))
+        if structure == "parallel":
+            self.cross_out = nn.Linear(d, 1)
+
+    def forward(self, dense: torch.Tensor, sparse: torch.Tensor) -> torch.Tensor:
+        d = self.cross_w.shape[1]
+        if self._use_fused_head(dense):
+            _, deep_in, partial = self._fused_head(dense, sparse,
+                                                   use_fm=False)
+        else:
+            e, lin = self._embed(sparse)
+            deep_in = torch.cat([e.flatten(1), dense], dim=1)
+            partial = self._first_order(dense, lin)
+        # a padded row goes to the fused MLP alone
+        unpad = (lambda t: t) if self.fused_mlp else (lambda t: t[:, :d])
+        if self.structure == "parallel":
+            logit = cross_network(deep_in, self.cross_w, self.cross_b,
+                                  self.cross_out.weight,
+                                  self.cross_out.bias, partial)
+            return self._dnn_out(unpad(deep_in), logit)
+        x_l = cross_network(deep_in, self.cross_w, self.cross_b)
+        return self._dnn_out(unpad(x_l), partial)
+
+
 def convert_mlp_bf16(model: _DNNHead) -> _DNNHead:
     """Native-bf16 MLP: the dnn's weights LIVE in bf16 (straight into MFMA
     GEMMs, no per-step autocast casts; the flat optimizer keeps an fp32
@@ -622,6 +677,15 @@ def convert_mlp_bf16(model: _DNNHead) -> _DNNHead:
               and seq[0].out_features <= 416)
         model.fused_mlp = ok
     model.head_bf16 = True
+    if hasattr(model, "cross_w"):
+        # the cross parameters live in bf16 like the dnn's; the kernels
+        # take a padded row up to 512 wide and up to 6 layers
+        for p in (model.cross_w, model.cross_b):
+            p.data = p.data.to(torch.bfloat16)
+        if hasattr(model, "cross_out"):
+            model.cross_out.to(torch.bfloat16)
+        L, d = model.cross_b.shape
+        model.fused_cross = (d + 31) // 32 * 32 <= 512 and L <= 6
     if hasattr(model, "cin"):
         # CIN layer GEMMs in bf16 (fp32 accumulation inside the library
         # GEMM); weights and outputs stay fp32
@@ -630,4 +694,4 @@ def convert_mlp_bf16(model: _DNNHead) -> _DNNHead:
 
 
 MODELS = {"lr": LR, "wdl": WDL, "deepfm": DeepFM, "xdeepfm": xDeepFM,
-          "dlrm": DLRM}
+          "dlrm": DLRM, "dcn": DCN}

@@ -121,6 +121,14 @@ void emb_dot_interact_fwd(const float*, const float*, void*, long, long,
 void emb_dot_interact_bwd(const float*, const float*, const void*, float*,
                           float*, long, long, long, long, int, int,
                           hipStream_t_);
+int emb_cross_fits(long, long, long, long);
+int emb_cross_bm(long, int);
+void emb_cross_fwd(const void*, const void*, const void*, long, long, long,
+                   long, void*, void*, int, const void*, const void*,
+                   const float*, float*, int, hipStream_t_);
+void emb_cross_bwd(const void*, const void*, const void*, long, long, long,
+                   long, const float*, const void*, const void*, void*,
+                   void*, int, hipStream_t_);
 void emb_mlp3_bias_bwd(const float*, const void*, const void*, const void*,
                        const void*, long, long, float*, void*, void*, void*,
                        void*, void*, int, int, hipStream_t_);
@@ -2090,6 +2098,139 @@ std::tuple<torch::Tensor, torch::Tensor> dot_interact_bwd(
     return {de, dx};
 }
 
+// ---- DCN-v2 cross network (cross.hip) -----------------------------------
+
+// Everything the kernels rely on, checked before a launch. The Python side
+// (ops.cross_network) tests the same limits and routes the rest to torch.
+// x0 [M, dp] bf16 with dp = ceil32(d), w an [L, dp, dp] stack of fragment-
+// major images (mlp3_pack_frag), b [L, d].
+static void cross_check(const torch::Tensor& x0, const torch::Tensor& w,
+                        const torch::Tensor& b, long bm, const char* who) {
+    TORCH_CHECK(x0.is_cuda() && w.is_cuda() && b.is_cuda()
+                && w.device() == x0.device() && b.device() == x0.device(),
+                who, ": operands must be on one GPU");
+    TORCH_CHECK(x0.scalar_type() == torch::kBFloat16
+                && w.scalar_type() == torch::kBFloat16
+                && b.scalar_type() == torch::kBFloat16, who,
+                ": x0, the weight images and b must be bf16");
+    TORCH_CHECK(x0.dim() == 2 && w.dim() == 3 && b.dim() == 2, who,
+                ": x0 [M, dp], images [L, dp, dp], b [L, d]");
+    TORCH_CHECK(x0.is_contiguous() && w.is_contiguous() && b.is_contiguous(),
+                who, ": operands must be contiguous");
+    const long M = x0.size(0), dp = x0.size(1), L = b.size(0), d = b.size(1);
+    TORCH_CHECK(emb_cross_fits(M, d, dp, L), who, ": needs dp = ceil32(d) in "
+                "32..512, 1 <= L <= 6 and M*dp*(L+1) < 2^31");
+    TORCH_CHECK(w.size(0) == L && w.size(1) == dp && w.size(2) == dp, who,
+                ": weight images must be [L, dp, dp]");
+    TORCH_CHECK(bm == 0 || bm == 16 || bm == 32, who,
+                ": bm must be 0, 16 or 32");
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(x0.data_ptr()) & 15) == 0
+                && (reinterpret_cast<uintptr_t>(w.data_ptr()) & 15) == 0,
+                who, ": x0 and the images must be 16-byte aligned");
+}
+
+// a mirror the kernels write: contiguous bf16 [n, M, dp] on x0's device
+static void cross_check_mirror(const torch::Tensor& t,
+                               const torch::Tensor& x0, long n,
+                               const char* who) {
+    TORCH_CHECK(t.is_cuda() && t.device() == x0.device()
+                && t.scalar_type() == torch::kBFloat16 && t.is_contiguous()
+                && t.dim() == 3 && t.size(0) == n && t.size(1) == x0.size(0)
+                && t.size(2) == x0.size(1)
+                && (reinterpret_cast<uintptr_t>(t.data_ptr()) & 7) == 0,
+                who, ": a mirror must be contiguous bf16 [", n, ", M, dp]");
+}
+
+static const void* cross_vec(const OptTensor& t, const torch::Tensor& x0,
+                             long n, const char* who) {
+    TORCH_CHECK(t.has_value() && t->is_cuda() && t->device() == x0.device()
+                && t->scalar_type() == torch::kBFloat16
+                && t->is_contiguous() && t->numel() == n, who,
+                ": w_out [d] and b_out [1] must be contiguous bf16");
+    return t->data_ptr();
+}
+
+// xs: [L, M, dp] (x_1 .. x_L, with us [L, M, dp]: a backward follows), or
+// [1, M, dp] (x_L alone), or none in the logit form. w_out given: the fp32
+// logit [M] is written to out.
+void cross_fwd(torch::Tensor x0, torch::Tensor wimg, torch::Tensor b,
+               OptTensor xs, OptTensor us, OptTensor w_out, OptTensor b_out,
+               OptTensor partial, OptTensor out, long bm) {
+    cross_check(x0, wimg, b, bm, "cross_fwd");
+    const long M = x0.size(0), dp = x0.size(1), L = b.size(0), d = b.size(1);
+    const bool save_all = us.has_value();
+    TORCH_CHECK(xs.has_value() || w_out.has_value(),
+                "cross_fwd: the x_L form needs xs");
+    if (save_all) cross_check_mirror(*us, x0, L, "cross_fwd");
+    TORCH_CHECK(!save_all || xs.has_value(), "cross_fwd: us needs xs");
+    if (xs.has_value())
+        cross_check_mirror(*xs, x0, save_all ? L : 1, "cross_fwd");
+    const void *wo = nullptr, *bo = nullptr;
+    const float* pp = nullptr;
+    float* op = nullptr;
+    if (w_out.has_value()) {
+        wo = cross_vec(w_out, x0, d, "cross_fwd");
+        bo = cross_vec(b_out, x0, 1, "cross_fwd");
+        TORCH_CHECK(out.has_value() && out->is_cuda()
+                    && out->device() == x0.device()
+                    && out->scalar_type() == torch::kFloat32
+                    && out->is_contiguous() && out->dim() == 1
+                    && out->size(0) == M,
+                    "cross_fwd: out must be contiguous fp32 [M]");
+        op = out->data_ptr<float>();
+        if (partial.has_value()) {
+            TORCH_CHECK(partial->is_cuda() && partial->device() == x0.device()
+                        && partial->scalar_type() == torch::kFloat32
+                        && partial->is_contiguous() && partial->numel() == M,
+                        "cross_fwd: partial must be contiguous fp32 [M]");
+            pp = partial->data_ptr<float>();
+        }
+    } else {
+        TORCH_CHECK(!partial.has_value() && !out.has_value()
+                    && !b_out.has_value(),
+                    "cross_fwd: b_out, partial and out belong to w_out");
+    }
+    const c10::cuda::CUDAGuard guard(x0.device());
+    emb_cross_fwd(x0.data_ptr(), wimg.data_ptr(), b.data_ptr(), M, d, dp, L,
+                  xs.has_value() ? xs->data_ptr() : nullptr,
+                  save_all ? us->data_ptr() : nullptr, save_all ? 1 : 0, wo,
+                  bo, pp, op, (int)bm, cur_stream());
+}
+
+// wtimg: images of W_l^T. g_L comes from (dout [M] fp32, w_out [d]) in the
+// logit form, else from gl [M, dp] bf16. Writes qs [L, M, dp], dx0 [M, dp].
+void cross_bwd(torch::Tensor x0, torch::Tensor us, torch::Tensor wtimg,
+               torch::Tensor b, OptTensor dout, OptTensor w_out, OptTensor gl,
+               torch::Tensor qs, torch::Tensor dx0, long bm) {
+    cross_check(x0, wtimg, b, bm, "cross_bwd");
+    const long M = x0.size(0), dp = x0.size(1), L = b.size(0), d = b.size(1);
+    cross_check_mirror(us, x0, L, "cross_bwd");
+    cross_check_mirror(qs, x0, L, "cross_bwd");
+    cross_check_mirror(dx0.unsqueeze(0), x0, 1, "cross_bwd");
+    TORCH_CHECK(dout.has_value() == w_out.has_value()
+                && dout.has_value() != gl.has_value(),
+                "cross_bwd: either (dout, w_out) or gl");
+    const float* dp_ = nullptr;
+    const void *wo = nullptr, *gp = nullptr;
+    if (dout.has_value()) {
+        TORCH_CHECK(dout->is_cuda() && dout->device() == x0.device()
+                    && dout->scalar_type() == torch::kFloat32
+                    && dout->is_contiguous() && dout->numel() == M,
+                    "cross_bwd: dout must be contiguous fp32 [M]");
+        dp_ = dout->data_ptr<float>();
+        wo = cross_vec(w_out, x0, d, "cross_bwd");
+    } else {
+        cross_check_mirror(gl->unsqueeze(0), x0, 1, "cross_bwd");
+        gp = gl->data_ptr();
+    }
+    const c10::cuda::CUDAGuard guard(x0.device());
+    emb_cross_bwd(x0.data_ptr(), us.data_ptr(), wtimg.data_ptr(), M, d, dp,
+                  L, dp_, wo, gp, qs.data_ptr(), dx0.data_ptr(), (int)bm,
+                  cur_stream());
+}
+
+long cross_bm(long M, long bm) { return emb_cross_bm(M, (int)bm); }
+
 // ---- CIN implicit-GEMM -------------------------------------------------
 
 torch::Tensor cin_fwd(torch::Tensor x0p, torch::Tensor xkp,
@@ -2636,6 +2777,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "DLRM interaction bwd: (de, dx) from d_out, one launch, no atomics",
           pybind11::arg("e"), pybind11::arg("x"), pybind11::arg("d_out"),
           pybind11::arg("pad32"));
+    m.def("cross_fwd", &cross_fwd,
+          "DCN-v2 cross network fwd: all L layers in one launch on MFMA; "
+          "writes the mirrors it is given and, with w_out, the fp32 logit",
+          pybind11::arg("x0"), pybind11::arg("wimg"), pybind11::arg("b"),
+          pybind11::arg("xs"), pybind11::arg("us"), pybind11::arg("w_out"),
+          pybind11::arg("b_out"), pybind11::arg("partial"),
+          pybind11::arg("out"), pybind11::arg("bm") = 0);
+    m.def("cross_bwd", &cross_bwd,
+          "DCN-v2 cross network dgrad chain: q_l [L, M, dp] and dx0 in one "
+          "launch, no atomics",
+          pybind11::arg("x0"), pybind11::arg("us"), pybind11::arg("wtimg"),
+          pybind11::arg("b"), pybind11::arg("dout"), pybind11::arg("w_out"),
+          pybind11::arg("gl"), pybind11::arg("qs"), pybind11::arg("dx0"),
+          pybind11::arg("bm") = 0);
+    m.def("cross_bm", &cross_bm,
+          "rows per block the cross kernels' launcher picks for M rows",
+          pybind11::arg("M"), pybind11::arg("bm") = 0);
     m.def("cin_fwd", &cin_fwd,
           "CIN layer forward: implicit outer-product MFMA GEMM");
     m.def("cin_dw", &cin_dw,

@@ -641,6 +641,185 @@ def dot_interact(e: torch.Tensor, x: torch.Tensor, out_bf16: bool = False,
     return _dot_interact_torch(e, x, out_bf16, pad32)
 
 
+# ------------------------------------------------- DCN-v2 cross network
+# x_{l+1} = x_0 * (W_l x_l + b_l) + x_l for l = 0 .. L-1, optionally followed
+# by the head w_out . x_L + b_out (+ partial). ops/csrc/cross.hip runs all L
+# layers in one launch each way; OEAMD_CROSS=0 keeps the torch route on the
+# GPU in the same build (A/B runs). Read once at import.
+_CROSS = os.environ.get("OEAMD_CROSS", "1") != "0"
+
+
+def _cross_torch(x0, W, b, w_out, b_out, partial):
+    """The definition of the operator: plain differentiable ops in the
+    parameters' dtype."""
+    L, d = b.shape
+    x0v = x0[:, :d].to(W.dtype)
+    x = x0v
+    for l in range(L):
+        x = x0v * torch.nn.functional.linear(x, W[l], b[l]) + x
+    if w_out is None:
+        x = x.to(x0.dtype)
+        return torch.nn.functional.pad(x, (0, x0.shape[1] - d))
+    out = (x @ w_out.reshape(-1, 1)).squeeze(1).float() + b_out.float()
+    return out if partial is None else out + partial
+
+
+def _cross_images(W: torch.Tensor, dp: int, with_t: bool, ext):
+    """The fragment-major images of W_l and (with_t) of W_l^T, padded to
+    [dp, dp], in two [L, dp, dp] buffers cached on the parameter and
+    rewritten every forward: one mlp3_pack_frag launch for both sets while
+    they are six matrices or fewer, else one per set."""
+    L = W.shape[0]
+    bufs = getattr(W, "_cross_bufs", None)
+    if (bufs is None or bufs["w"].shape != (L, dp, dp)
+            or bufs["w"].device != W.device):
+        bufs = {k: torch.empty(L, dp, dp, dtype=torch.bfloat16,
+                               device=W.device) for k in ("w", "wt")}
+        W._cross_bufs = bufs
+    srcs = [W[l] for l in range(L)]
+    fwd = [bufs["w"][l] for l in range(L)]
+    if not with_t:
+        ext.mlp3_pack_frag(srcs, fwd, [False] * L)
+    elif 2 * L <= 6:
+        ext.mlp3_pack_frag(srcs + srcs, fwd + [bufs["wt"][l]
+                                               for l in range(L)],
+                           [False] * L + [True] * L)
+    else:
+        ext.mlp3_pack_frag(srcs, fwd, [False] * L)
+        ext.mlp3_pack_frag(srcs, [bufs["wt"][l] for l in range(L)],
+                           [True] * L)
+    return bufs
+
+
+class _CrossNetFn(torch.autograd.Function):
+    """k_cross_fwd / k_cross_bwd. Saved for the backward: x_0, the kernel's
+    mirrors x_1 .. x_L and u_0 .. u_{L-1}, and the transposed weight images
+    packed by the forward (the weights cannot change before the backward
+    runs). The kernel gives dx0 and q_l; dW_l = q_l^T x_l, db_l = sum_m q_l
+    and the head's gradients are library ops. When every parameter's .grad
+    is bound (the flat optimizer's views) they accumulate in place and
+    autograd gets None, as in _FusedMLP3Fn."""
+
+    @staticmethod
+    def forward(ctx, x0, W, b, w_out, b_out, partial, save, bm):
+        ext = require_hip()
+        M, dp = x0.shape
+        L = b.shape[0]
+        logit = w_out is not None
+        save = bool(save) and any(ctx.needs_input_grad)
+        W = W.contiguous()
+        b = b.contiguous()
+        bufs = _cross_images(W, dp, save, ext)
+        new = lambda *s, dt=torch.bfloat16: torch.empty(  # noqa: E731
+            *s, dtype=dt, device=x0.device)
+        us = new(L, M, dp) if save else None
+        xs = new(L, M, dp) if save else None if logit else new(1, M, dp)
+        out = new(M, dt=torch.float32) if logit else None
+        wo = w_out.reshape(-1).contiguous() if logit else None
+        ext.cross_fwd(x0, bufs["w"], b, xs, us, wo,
+                      b_out.reshape(-1).contiguous() if logit else None,
+                      partial.contiguous() if partial is not None else None,
+                      out, bm)
+        if save:
+            ctx.save_for_backward(x0, xs, us, b, wo)
+            ctx.bufs = bufs
+            ctx.bm = bm
+            ctx._params = (W, b, w_out, b_out)
+            ctx._has_partial = partial is not None
+        return out if logit else xs[-1]
+
+    @staticmethod
+    def backward(ctx, g):
+        ext = require_hip()
+        x0, xs, us, b, wo = ctx.saved_tensors
+        W, _, w_out, b_out = ctx._params
+        L, d = b.shape
+        logit = wo is not None
+        qs = torch.empty_like(us)
+        dx0 = torch.empty_like(x0)
+        dout = g.contiguous().float() if logit else None
+        gl = None if logit else g.to(torch.bfloat16).contiguous()
+        ext.cross_bwd(x0, us, ctx.bufs["wt"], b, dout, wo, gl, qs, dx0,
+                      ctx.bm)
+        xl = [x0[:, :d]] + [xs[l][:, :d] for l in range(L - 1)]
+        q = qs[:, :, :d]
+        params = [p for p in ctx._params if p is not None]
+        prebound = all(p.is_leaf and p.requires_grad and p.grad is not None
+                       and p.grad.dtype == torch.bfloat16
+                       and p.grad.is_contiguous() for p in params)
+        dpart = dout if ctx._has_partial else None
+        dvec = dout.to(torch.bfloat16).unsqueeze(0) if logit else None
+        if prebound:
+            for l in range(L):
+                W.grad[l].addmm_(q[l].t(), xl[l])
+            b.grad.add_(q.sum(1))
+            if logit:
+                w_out.grad.view(1, d).addmm_(dvec, xs[L - 1][:, :d])
+                b_out.grad.add_(dout.sum().to(b_out.grad.dtype))
+            return dx0, None, None, None, None, dpart, None, None
+        need = ctx.needs_input_grad
+        dW = db = dwo = dbo = None
+        if need[1]:
+            dW = torch.stack([q[l].t() @ xl[l] for l in range(L)])
+        if need[2]:
+            db = q.sum(1)
+        if logit and need[3]:
+            dwo = (dvec @ xs[L - 1][:, :d]).view_as(w_out)
+        if logit and need[4]:
+            dbo = dout.sum().to(b_out.dtype).view_as(b_out)
+        return dx0, dW, db, dwo, dbo, dpart, None, None
+
+
+def _cross_fits(x0, W, b, w_out, b_out, partial) -> bool:
+    """The limits the binding checks (it refuses everything else)."""
+    bf = torch.bfloat16
+    if not (_use_hip(x0) and x0.dtype == W.dtype == b.dtype == bf
+            and x0.is_contiguous() and W.device == b.device == x0.device):
+        return False
+    M, dp = x0.shape
+    L, d = b.shape
+    if not (dp == (d + 31) // 32 * 32 and 32 <= dp <= 512 and 1 <= L <= 6
+            and M * dp * (L + 1) < 2 ** 31 and x0.data_ptr() % 16 == 0):
+        return False
+    if w_out is None:
+        return True
+    return (w_out.dtype == b_out.dtype == bf
+            and w_out.device == b_out.device == x0.device
+            and (partial is None or (partial.dtype == torch.float32
+                                     and partial.device == x0.device)))
+
+
+def cross_network(x0: torch.Tensor, W: torch.Tensor, b: torch.Tensor,
+                  w_out: torch.Tensor = None, b_out: torch.Tensor = None,
+                  partial: torch.Tensor = None, bm: int = 0) -> torch.Tensor:
+    """DCN-v2 cross network, differentiable w.r.t. every tensor argument.
+
+    x0 [M, d], or [M, ceil32(d)] with zero pad columns; W [L, d, d], each
+    W[l] stored [out, in] like nn.Linear; b [L, d]. Computes
+    x_{l+1} = x_0 * (W_l x_l + b_l) + x_l for l = 0 .. L-1 and returns x_L in
+    x0's shape and dtype, or with w_out [d] and b_out [1] the fp32 logit [M]
+    = w_out . x_L + b_out (+ partial [M]).
+
+    GPU: one HIP launch each way (ops/csrc/cross.hip) for contiguous bf16
+    x0 [M, dp], dp = ceil32(d) in 32..512, bf16 parameters, 1 <= L <= 6 and
+    M*dp*(L+1) < 2^31: bf16 operands, fp32 arithmetic, each stored value
+    rounded to bf16 once. Everything else, and the CPU, takes torch ops in
+    the parameters' dtype. ``bm`` forces the kernels' row tile (16 or 32;
+    0 = the launcher's choice)."""
+    if (x0.dim() != 2 or W.dim() != 3 or b.dim() != 2
+            or W.shape != (b.shape[0], b.shape[1], b.shape[1])
+            or x0.shape[1] not in (b.shape[1], (b.shape[1] + 31) // 32 * 32)
+            or (w_out is None) != (b_out is None)
+            or (partial is not None and w_out is None)):
+        raise ValueError("cross_network takes x0 [M, d or ceil32(d)], "
+                         "W [L, d, d], b [L, d], w_out [d] with b_out [1]")
+    if (_CROSS and _cross_fits(x0, W, b, w_out, b_out, partial)
+            and require_hip() is not None):
+        return _CrossNetFn.apply(x0, W, b, w_out, b_out, partial,
+                                 torch.is_grad_enabled(), bm)
+    return _cross_torch(x0, W, b, w_out, b_out, partial)
+
+
 # ----------------------------------------------------------------- fused loss
 
 class _FusedBCEFn(torch.autograd.Function):

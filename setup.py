@@ -24,6 +24,7 @@ ext = CUDAExtension(
         "openembedding_amd/ops/csrc/mlp.hip",
         "openembedding_amd/ops/csrc/cin.hip",
         "openembedding_amd/ops/csrc/dlrm.hip",
+        "openembedding_amd/ops/csrc/cross.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3"],
