@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from ..ops import hip_available
-from ..ops.dispatch import cross_network, dot_interact
+from ..ops.dispatch import cross_network, cross_network_lr, dot_interact
 from ..torch import CombinedEmbedding
 from .criteo import CRITEO_FIELD_VOCABS, N_DENSE
 
@@ -618,12 +618,19 @@ class DCN(_CTRBase):
     on the head's 32-padded bf16 row - in the parallel structure with the
     cross logit computed by the kernel and carried on as the fused MLP's
     ``partial``, in the stacked one emitting the padded bf16 row that the
-    fused MLP consumes. Otherwise, and on the CPU, torch ops."""
+    fused MLP consumes. Otherwise, and on the CPU, torch ops.
+
+    ``low_rank=r`` (1 <= r < d) gives the paper's production variant
+    W_l = U_l V_l: ``cross_u`` [L, d, r] and ``cross_v`` [L, r, d] replace
+    ``cross_w`` and the cross network is ``ops.cross_network_lr``
+    (ops/csrc/cross_lr.hip, ceil32(r) <= 128). No mixture of experts, no
+    gate, no non-linearity inside the projection."""
 
     def __init__(self, field_vocabs: Optional[List[int]] = None, dim: int = 9,
                  cross_layers: int = 3,
                  hidden: Sequence[int] = (400, 400, 400),
-                 structure: str = "parallel", **kw):
+                 structure: str = "parallel",
+                 low_rank: Optional[int] = None, **kw):
         super().__init__(field_vocabs, dim, **kw)
         if structure not in ("parallel", "stacked"):
             raise ValueError("structure must be 'parallel' or 'stacked'")
@@ -632,15 +639,29 @@ class DCN(_CTRBase):
         self.structure = structure
         d = self.n_fields * dim + N_DENSE
         self.dnn = _mlp(d, hidden)
-        self.cross_w = nn.Parameter(torch.empty(cross_layers, d, d))
-        for w in self.cross_w:
-            nn.init.xavier_uniform_(w)
+        if low_rank is None:
+            self.cross_w = nn.Parameter(torch.empty(cross_layers, d, d))
+            for w in self.cross_w:
+                nn.init.xavier_uniform_(w)
+        else:
+            if not 1 <= low_rank < d:
+                raise ValueError("low_rank must be in 1 .. d - 1")
+            self.cross_u = nn.Parameter(
+                torch.empty(cross_layers, d, low_rank))
+            self.cross_v = nn.Parameter(
+                torch.empty(cross_layers, low_rank, d))
+            for w in list(self.cross_u) + list(self.cross_v):
+                nn.init.xavier_uniform_(w)
         self.cross_b = nn.Parameter(torch.zeros(cross_layers, d))
         if structure == "parallel":
             self.cross_out = nn.Linear(d, 1)
 
     def forward(self, dense: torch.Tensor, sparse: torch.Tensor) -> torch.Tensor:
-        d = self.cross_w.shape[1]
+        d = self.cross_b.shape[1]
+        if hasattr(self, "cross_w"):
+            cross, ws = cross_network, (self.cross_w,)
+        else:
+            cross, ws = cross_network_lr, (self.cross_u, self.cross_v)
         if self._use_fused_head(dense):
             _, deep_in, partial = self._fused_head(dense, sparse,
                                                    use_fm=False)
@@ -651,11 +672,10 @@ class DCN(_CTRBase):
         # a padded row goes to the fused MLP alone
         unpad = (lambda t: t) if self.fused_mlp else (lambda t: t[:, :d])
         if self.structure == "parallel":
-            logit = cross_network(deep_in, self.cross_w, self.cross_b,
-                                  self.cross_out.weight,
-                                  self.cross_out.bias, partial)
+            logit = cross(deep_in, *ws, self.cross_b, self.cross_out.weight,
+                          self.cross_out.bias, partial)
             return self._dnn_out(unpad(deep_in), logit)
-        x_l = cross_network(deep_in, self.cross_w, self.cross_b)
+        x_l = cross(deep_in, *ws, self.cross_b)
         return self._dnn_out(unpad(x_l), partial)
 
 
@@ -677,15 +697,19 @@ def convert_mlp_bf16(model: _DNNHead) -> _DNNHead:
               and seq[0].out_features <= 416)
         model.fused_mlp = ok
     model.head_bf16 = True
-    if hasattr(model, "cross_w"):
+    if hasattr(model, "cross_b"):
         # the cross parameters live in bf16 like the dnn's; the kernels
-        # take a padded row up to 512 wide and up to 6 layers
-        for p in (model.cross_w, model.cross_b):
+        # take a padded row up to 512 wide and up to 6 layers, the low-rank
+        # ones a padded rank up to 128
+        low_rank = not hasattr(model, "cross_w")
+        ws = (model.cross_u, model.cross_v) if low_rank else (model.cross_w,)
+        for p in ws + (model.cross_b,):
             p.data = p.data.to(torch.bfloat16)
         if hasattr(model, "cross_out"):
             model.cross_out.to(torch.bfloat16)
         L, d = model.cross_b.shape
-        model.fused_cross = (d + 31) // 32 * 32 <= 512 and L <= 6
+        model.fused_cross = (d + 31) // 32 * 32 <= 512 and L <= 6 and (
+            not low_rank or (model.cross_v.shape[1] + 31) // 32 * 32 <= 128)
     if hasattr(model, "cin"):
         # CIN layer GEMMs in bf16 (fp32 accumulation inside the library
         # GEMM); weights and outputs stay fp32

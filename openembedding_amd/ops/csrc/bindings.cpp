@@ -129,6 +129,16 @@ void emb_cross_fwd(const void*, const void*, const void*, long, long, long,
 void emb_cross_bwd(const void*, const void*, const void*, long, long, long,
                    long, const float*, const void*, const void*, void*,
                    void*, int, hipStream_t_);
+int emb_cross_lr_fits(long, long, long, long, long, long);
+int emb_cross_lr_bm(long, int);
+void emb_cross_lr_fwd(const void*, const void*, const void*, const void*,
+                      long, long, long, long, long, long, void*, void*,
+                      void*, int, const void*, const void*, const float*,
+                      float*, int, hipStream_t_);
+void emb_cross_lr_bwd(const void*, const void*, const void*, const void*,
+                      long, long, long, long, long, long, const float*,
+                      const void*, const void*, void*, void*, void*, int,
+                      hipStream_t_);
 void emb_mlp3_bias_bwd(const float*, const void*, const void*, const void*,
                        const void*, long, long, float*, void*, void*, void*,
                        void*, void*, int, int, hipStream_t_);
@@ -2231,6 +2241,154 @@ void cross_bwd(torch::Tensor x0, torch::Tensor us, torch::Tensor wtimg,
 
 long cross_bm(long M, long bm) { return emb_cross_bm(M, (int)bm); }
 
+// ---- DCN-v2 low-rank cross network (cross_lr.hip) -----------------------
+
+// x0 [M, dp] bf16 with dp = ceil32(d); down: an [L, rp, dp] stack of
+// fragment-major images (V_l forward, U_l^T backward), up: [L, dp, rp]
+// (U_l forward, V_l^T backward), rp = ceil32(r); b [L, d]. ops.
+// cross_network_lr tests the same limits and routes the rest to torch.
+static void cross_lr_check(const torch::Tensor& x0, const torch::Tensor& down,
+                           const torch::Tensor& up, const torch::Tensor& b,
+                           long r, long bm, const char* who) {
+    TORCH_CHECK(x0.is_cuda() && down.is_cuda() && up.is_cuda() && b.is_cuda()
+                && down.device() == x0.device() && up.device() == x0.device()
+                && b.device() == x0.device(),
+                who, ": operands must be on one GPU");
+    TORCH_CHECK(x0.scalar_type() == torch::kBFloat16
+                && down.scalar_type() == torch::kBFloat16
+                && up.scalar_type() == torch::kBFloat16
+                && b.scalar_type() == torch::kBFloat16, who,
+                ": x0, the weight images and b must be bf16");
+    TORCH_CHECK(x0.dim() == 2 && down.dim() == 3 && up.dim() == 3
+                && b.dim() == 2, who,
+                ": x0 [M, dp], images [L, rp, dp] and [L, dp, rp], b [L, d]");
+    TORCH_CHECK(x0.is_contiguous() && down.is_contiguous()
+                && up.is_contiguous() && b.is_contiguous(),
+                who, ": operands must be contiguous");
+    const long M = x0.size(0), dp = x0.size(1), L = b.size(0), d = b.size(1);
+    const long rp = down.size(1);
+    TORCH_CHECK(emb_cross_lr_fits(M, d, dp, r, rp, L), who, ": needs dp = "
+                "ceil32(d) in 32..512, rp = ceil32(r) in 32..128, "
+                "1 <= L <= 6 and M*max(dp, rp)*(L+1) < 2^31");
+    TORCH_CHECK(down.size(0) == L && down.size(2) == dp && up.size(0) == L
+                && up.size(1) == dp && up.size(2) == rp, who,
+                ": weight images must be [L, rp, dp] and [L, dp, rp]");
+    TORCH_CHECK(bm == 0 || bm == 16 || bm == 32, who,
+                ": bm must be 0, 16 or 32");
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(x0.data_ptr()) & 15) == 0
+                && (reinterpret_cast<uintptr_t>(down.data_ptr()) & 15) == 0
+                && (reinterpret_cast<uintptr_t>(up.data_ptr()) & 15) == 0,
+                who, ": x0 and the images must be 16-byte aligned");
+}
+
+// a rank mirror the kernels write in 16-byte pieces: bf16 [L, M, rp]
+static void cross_lr_check_rank(const torch::Tensor& t,
+                                const torch::Tensor& x0, long L, long rp,
+                                const char* who) {
+    TORCH_CHECK(t.is_cuda() && t.device() == x0.device()
+                && t.scalar_type() == torch::kBFloat16 && t.is_contiguous()
+                && t.dim() == 3 && t.size(0) == L && t.size(1) == x0.size(0)
+                && t.size(2) == rp
+                && (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0,
+                who, ": a rank mirror must be contiguous bf16 [L, M, rp], "
+                "16-byte aligned");
+}
+
+// xs: [L, M, dp] (x_1 .. x_L, with us [L, M, dp] and ps [L, M, rp]: a
+// backward follows), or [1, M, dp] (x_L alone), or none in the logit form.
+// w_out given: the fp32 logit [M] is written to out.
+void cross_lr_fwd(torch::Tensor x0, torch::Tensor vimg, torch::Tensor uimg,
+                  torch::Tensor b, long r, OptTensor xs, OptTensor us,
+                  OptTensor ps, OptTensor w_out, OptTensor b_out,
+                  OptTensor partial, OptTensor out, long bm) {
+    cross_lr_check(x0, vimg, uimg, b, r, bm, "cross_lr_fwd");
+    const long M = x0.size(0), dp = x0.size(1), L = b.size(0), d = b.size(1);
+    const long rp = vimg.size(1);
+    const bool save_all = us.has_value();
+    TORCH_CHECK(xs.has_value() || w_out.has_value(),
+                "cross_lr_fwd: the x_L form needs xs");
+    TORCH_CHECK(save_all == ps.has_value() && (!save_all || xs.has_value()),
+                "cross_lr_fwd: us, ps and xs [L, M, dp] come together");
+    if (save_all) {
+        cross_check_mirror(*us, x0, L, "cross_lr_fwd");
+        cross_lr_check_rank(*ps, x0, L, rp, "cross_lr_fwd");
+    }
+    if (xs.has_value())
+        cross_check_mirror(*xs, x0, save_all ? L : 1, "cross_lr_fwd");
+    const void *wo = nullptr, *bo = nullptr;
+    const float* pp = nullptr;
+    float* op = nullptr;
+    if (w_out.has_value()) {
+        wo = cross_vec(w_out, x0, d, "cross_lr_fwd");
+        bo = cross_vec(b_out, x0, 1, "cross_lr_fwd");
+        TORCH_CHECK(out.has_value() && out->is_cuda()
+                    && out->device() == x0.device()
+                    && out->scalar_type() == torch::kFloat32
+                    && out->is_contiguous() && out->dim() == 1
+                    && out->size(0) == M,
+                    "cross_lr_fwd: out must be contiguous fp32 [M]");
+        op = out->data_ptr<float>();
+        if (partial.has_value()) {
+            TORCH_CHECK(partial->is_cuda() && partial->device() == x0.device()
+                        && partial->scalar_type() == torch::kFloat32
+                        && partial->is_contiguous() && partial->numel() == M,
+                        "cross_lr_fwd: partial must be contiguous fp32 [M]");
+            pp = partial->data_ptr<float>();
+        }
+    } else {
+        TORCH_CHECK(!partial.has_value() && !out.has_value()
+                    && !b_out.has_value(),
+                    "cross_lr_fwd: b_out, partial and out belong to w_out");
+    }
+    const c10::cuda::CUDAGuard guard(x0.device());
+    emb_cross_lr_fwd(x0.data_ptr(), vimg.data_ptr(), uimg.data_ptr(),
+                     b.data_ptr(), M, d, dp, r, rp, L,
+                     xs.has_value() ? xs->data_ptr() : nullptr,
+                     save_all ? us->data_ptr() : nullptr,
+                     save_all ? ps->data_ptr() : nullptr, save_all ? 1 : 0,
+                     wo, bo, pp, op, (int)bm, cur_stream());
+}
+
+// utimg: images of U_l^T [L, rp, dp], vtimg: of V_l^T [L, dp, rp]. g_L comes
+// from (dout [M] fp32, w_out [d]) in the logit form, else from gl [M, dp]
+// bf16. Writes qs [L, M, dp], ss [L, M, rp], dx0 [M, dp].
+void cross_lr_bwd(torch::Tensor x0, torch::Tensor us, torch::Tensor utimg,
+                  torch::Tensor vtimg, torch::Tensor b, long r,
+                  OptTensor dout, OptTensor w_out, OptTensor gl,
+                  torch::Tensor qs, torch::Tensor ss, torch::Tensor dx0,
+                  long bm) {
+    cross_lr_check(x0, utimg, vtimg, b, r, bm, "cross_lr_bwd");
+    const long M = x0.size(0), dp = x0.size(1), L = b.size(0), d = b.size(1);
+    const long rp = utimg.size(1);
+    cross_check_mirror(us, x0, L, "cross_lr_bwd");
+    cross_check_mirror(qs, x0, L, "cross_lr_bwd");
+    cross_lr_check_rank(ss, x0, L, rp, "cross_lr_bwd");
+    cross_check_mirror(dx0.unsqueeze(0), x0, 1, "cross_lr_bwd");
+    TORCH_CHECK(dout.has_value() == w_out.has_value()
+                && dout.has_value() != gl.has_value(),
+                "cross_lr_bwd: either (dout, w_out) or gl");
+    const float* dp_ = nullptr;
+    const void *wo = nullptr, *gp = nullptr;
+    if (dout.has_value()) {
+        TORCH_CHECK(dout->is_cuda() && dout->device() == x0.device()
+                    && dout->scalar_type() == torch::kFloat32
+                    && dout->is_contiguous() && dout->numel() == M,
+                    "cross_lr_bwd: dout must be contiguous fp32 [M]");
+        dp_ = dout->data_ptr<float>();
+        wo = cross_vec(w_out, x0, d, "cross_lr_bwd");
+    } else {
+        cross_check_mirror(gl->unsqueeze(0), x0, 1, "cross_lr_bwd");
+        gp = gl->data_ptr();
+    }
+    const c10::cuda::CUDAGuard guard(x0.device());
+    emb_cross_lr_bwd(x0.data_ptr(), us.data_ptr(), utimg.data_ptr(),
+                     vtimg.data_ptr(), M, d, dp, r, rp, L, dp_, wo, gp,
+                     qs.data_ptr(), ss.data_ptr(), dx0.data_ptr(), (int)bm,
+                     cur_stream());
+}
+
+long cross_lr_bm(long M, long bm) { return emb_cross_lr_bm(M, (int)bm); }
+
 // ---- CIN implicit-GEMM -------------------------------------------------
 
 torch::Tensor cin_fwd(torch::Tensor x0p, torch::Tensor xkp,
@@ -2793,6 +2951,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("bm") = 0);
     m.def("cross_bm", &cross_bm,
           "rows per block the cross kernels' launcher picks for M rows",
+          pybind11::arg("M"), pybind11::arg("bm") = 0);
+    m.def("cross_lr_fwd", &cross_lr_fwd,
+          "DCN-v2 low-rank cross network fwd: all L layers in one launch on "
+          "MFMA; writes the mirrors it is given and, with w_out, the logit",
+          pybind11::arg("x0"), pybind11::arg("vimg"), pybind11::arg("uimg"),
+          pybind11::arg("b"), pybind11::arg("r"), pybind11::arg("xs"),
+          pybind11::arg("us"), pybind11::arg("ps"), pybind11::arg("w_out"),
+          pybind11::arg("b_out"), pybind11::arg("partial"),
+          pybind11::arg("out"), pybind11::arg("bm") = 0);
+    m.def("cross_lr_bwd", &cross_lr_bwd,
+          "DCN-v2 low-rank cross network dgrad chain: q_l [L, M, dp], s_l "
+          "[L, M, rp] and dx0 in one launch, no atomics",
+          pybind11::arg("x0"), pybind11::arg("us"), pybind11::arg("utimg"),
+          pybind11::arg("vtimg"), pybind11::arg("b"), pybind11::arg("r"),
+          pybind11::arg("dout"), pybind11::arg("w_out"), pybind11::arg("gl"),
+          pybind11::arg("qs"), pybind11::arg("ss"), pybind11::arg("dx0"),
+          pybind11::arg("bm") = 0);
+    m.def("cross_lr_bm", &cross_lr_bm,
+          "rows per block the low-rank cross kernels' launcher picks",
           pybind11::arg("M"), pybind11::arg("bm") = 0);
     m.def("cin_fwd", &cin_fwd,
           "CIN layer forward: implicit outer-product MFMA GEMM");

@@ -820,6 +820,203 @@ def cross_network(x0: torch.Tensor, W: torch.Tensor, b: torch.Tensor,
     return _cross_torch(x0, W, b, w_out, b_out, partial)
 
 
+# --------------------------------------- DCN-v2 low-rank cross network
+# x_{l+1} = x_0 * (U_l (V_l x_l) + b_l) + x_l: W_l = U_l V_l of rank r << d.
+# ops/csrc/cross_lr.hip runs all L layers in one launch each way;
+# OEAMD_CROSS_LR=0 keeps the torch route on the GPU in the same build (A/B
+# runs). Read once at import.
+_CROSS_LR = os.environ.get("OEAMD_CROSS_LR", "1") != "0"
+
+
+def _cross_lr_torch(x0, U, V, b, w_out, b_out, partial):
+    """The definition of the operator: plain differentiable ops in the
+    parameters' dtype."""
+    L, d = b.shape
+    x0v = x0[:, :d].to(U.dtype)
+    x = x0v
+    lin = torch.nn.functional.linear
+    for l in range(L):
+        x = x0v * lin(lin(x, V[l]), U[l], b[l]) + x
+    if w_out is None:
+        x = x.to(x0.dtype)
+        return torch.nn.functional.pad(x, (0, x0.shape[1] - d))
+    out = (x @ w_out.reshape(-1, 1)).squeeze(1).float() + b_out.float()
+    return out if partial is None else out + partial
+
+
+def _cross_lr_images(U: torch.Tensor, V: torch.Tensor, dp: int, rp: int,
+                     with_t: bool, ext):
+    """The fragment-major images of V_l [rp, dp] and U_l [dp, rp], and
+    (with_t) of U_l^T [rp, dp] and V_l^T [dp, rp], zero-padded, in buffers
+    cached on U and rewritten every forward by mlp3_pack_frag, six matrices
+    per launch."""
+    L = U.shape[0]
+    bufs = getattr(U, "_cross_lr_bufs", None)
+    if (bufs is None or bufs["v"].shape != (L, rp, dp)
+            or bufs["v"].device != U.device):
+        new = lambda *s: torch.empty(*s, dtype=torch.bfloat16,  # noqa: E731
+                                     device=U.device)
+        bufs = {"v": new(L, rp, dp), "u": new(L, dp, rp),
+                "ut": new(L, rp, dp), "vt": new(L, dp, rp)}
+        U._cross_lr_bufs = bufs
+    jobs = []
+    for l in range(L):
+        jobs += [(V[l], bufs["v"][l], False), (U[l], bufs["u"][l], False)]
+    for l in range(L if with_t else 0):
+        jobs += [(U[l], bufs["ut"][l], True), (V[l], bufs["vt"][l], True)]
+    for i in range(0, len(jobs), 6):
+        src, dst, tr = zip(*jobs[i:i + 6])
+        ext.mlp3_pack_frag(list(src), list(dst), list(tr))
+    return bufs
+
+
+class _CrossLRFn(torch.autograd.Function):
+    """k_cross_lr_fwd / k_cross_lr_bwd. Saved for the backward: x_0, the
+    kernel's mirrors x_1 .. x_L, u_l and p_l, and the transposed weight
+    images packed by the forward. The kernel gives dx0, q_l and s_l;
+    dU_l = q_l^T p_l, dV_l = s_l^T x_l, db_l = sum_m q_l and the head's
+    gradients are library ops. When every parameter's .grad is bound they
+    accumulate in place and autograd gets None, as in _CrossNetFn."""
+
+    @staticmethod
+    def forward(ctx, x0, U, V, b, w_out, b_out, partial, save, bm):
+        ext = require_hip()
+        M, dp = x0.shape
+        L, r = V.shape[0], V.shape[1]
+        rp = (r + 31) // 32 * 32
+        logit = w_out is not None
+        save = bool(save) and any(ctx.needs_input_grad)
+        U, V, b = U.contiguous(), V.contiguous(), b.contiguous()
+        bufs = _cross_lr_images(U, V, dp, rp, save, ext)
+        new = lambda *s, dt=torch.bfloat16: torch.empty(  # noqa: E731
+            *s, dtype=dt, device=x0.device)
+        us = new(L, M, dp) if save else None
+        ps = new(L, M, rp) if save else None
+        xs = new(L, M, dp) if save else None if logit else new(1, M, dp)
+        out = new(M, dt=torch.float32) if logit else None
+        wo = w_out.reshape(-1).contiguous() if logit else None
+        ext.cross_lr_fwd(x0, bufs["v"], bufs["u"], b, r, xs, us, ps, wo,
+                         b_out.reshape(-1).contiguous() if logit else None,
+                         partial.contiguous() if partial is not None
+                         else None, out, bm)
+        if save:
+            ctx.save_for_backward(x0, xs, us, ps, b, wo)
+            ctx.bufs = bufs
+            ctx.bm = bm
+            ctx._params = (U, V, b, w_out, b_out)
+            ctx._has_partial = partial is not None
+        return out if logit else xs[-1]
+
+    @staticmethod
+    def backward(ctx, g):
+        ext = require_hip()
+        x0, xs, us, ps, b, wo = ctx.saved_tensors
+        U, V, _, w_out, b_out = ctx._params
+        L, d = b.shape
+        r = V.shape[1]
+        logit = wo is not None
+        qs = torch.empty_like(us)
+        ss = torch.empty_like(ps)
+        dx0 = torch.empty_like(x0)
+        dout = g.contiguous().float() if logit else None
+        gl = None if logit else g.to(torch.bfloat16).contiguous()
+        ext.cross_lr_bwd(x0, us, ctx.bufs["ut"], ctx.bufs["vt"], b, r, dout,
+                         wo, gl, qs, ss, dx0, ctx.bm)
+        xl = [x0[:, :d]] + [xs[l][:, :d] for l in range(L - 1)]
+        q, s, p = qs[:, :, :d], ss[:, :, :r], ps[:, :, :r]
+        params = [t for t in ctx._params if t is not None]
+        prebound = all(t.is_leaf and t.requires_grad and t.grad is not None
+                       and t.grad.dtype == torch.bfloat16
+                       and t.grad.is_contiguous() for t in params)
+        dpart = dout if ctx._has_partial else None
+        dvec = dout.to(torch.bfloat16).unsqueeze(0) if logit else None
+        if prebound:
+            for l in range(L):
+                U.grad[l].addmm_(q[l].t(), p[l])
+                V.grad[l].addmm_(s[l].t(), xl[l])
+            b.grad.add_(q.sum(1))
+            if logit:
+                w_out.grad.view(1, d).addmm_(dvec, xs[L - 1][:, :d])
+                b_out.grad.add_(dout.sum().to(b_out.grad.dtype))
+            return dx0, None, None, None, None, None, dpart, None, None
+        need = ctx.needs_input_grad
+        dU = dV = db = dwo = dbo = None
+        if need[1]:
+            dU = torch.stack([q[l].t() @ p[l] for l in range(L)])
+        if need[2]:
+            dV = torch.stack([s[l].t() @ xl[l] for l in range(L)])
+        if need[3]:
+            db = q.sum(1)
+        if logit and need[4]:
+            dwo = (dvec @ xs[L - 1][:, :d]).view_as(w_out)
+        if logit and need[5]:
+            dbo = dout.sum().to(b_out.dtype).view_as(b_out)
+        return dx0, dU, dV, db, dwo, dbo, dpart, None, None
+
+
+def _cross_lr_fits(x0, U, V, b, w_out, b_out, partial) -> bool:
+    """The limits the binding checks (it refuses everything else)."""
+    bf = torch.bfloat16
+    if not (_use_hip(x0) and x0.dtype == U.dtype == V.dtype == b.dtype == bf
+            and x0.is_contiguous()
+            and U.device == V.device == b.device == x0.device):
+        return False
+    M, dp = x0.shape
+    L, d = b.shape
+    rp = (V.shape[1] + 31) // 32 * 32
+    if not (dp == (d + 31) // 32 * 32 and 32 <= dp <= 512 and rp <= 128
+            and 1 <= L <= 6 and M * max(dp, rp) * (L + 1) < 2 ** 31
+            and x0.data_ptr() % 16 == 0):
+        return False
+    if w_out is None:
+        return True
+    return (w_out.dtype == b_out.dtype == bf
+            and w_out.device == b_out.device == x0.device
+            and (partial is None or (partial.dtype == torch.float32
+                                     and partial.device == x0.device)))
+
+
+def cross_network_lr(x0: torch.Tensor, U: torch.Tensor, V: torch.Tensor,
+                     b: torch.Tensor, w_out: torch.Tensor = None,
+                     b_out: torch.Tensor = None,
+                     partial: torch.Tensor = None,
+                     bm: int = 0) -> torch.Tensor:
+    """DCN-v2 cross network with low-rank layers W_l = U_l V_l,
+    differentiable w.r.t. every tensor argument.
+
+    x0 [M, d], or [M, ceil32(d)] with zero pad columns; V [L, r, d] the
+    down-projection and U [L, d, r] the up-projection, each stored
+    [out, in] like nn.Linear; b [L, d]. Computes
+    x_{l+1} = x_0 * (U_l (V_l x_l) + b_l) + x_l for l = 0 .. L-1 and returns
+    x_L in x0's shape and dtype, or with w_out [d] and b_out [1] the fp32
+    logit [M] = w_out . x_L + b_out (+ partial [M]): ``cross_network``'s two
+    forms. Out of scope: the paper's mixture of experts with its gate, and
+    the non-linearity inside the projection.
+
+    GPU: one HIP launch each way (ops/csrc/cross_lr.hip) for contiguous bf16
+    x0 [M, dp], dp = ceil32(d) in 32..512, rp = ceil32(r) <= 128, bf16
+    parameters, 1 <= L <= 6 and M*max(dp, rp)*(L+1) < 2^31: bf16 operands,
+    fp32 arithmetic, each stored value (the rank activation included)
+    rounded to bf16 once. Everything else, and the CPU, takes torch ops in
+    the parameters' dtype. ``bm`` forces the kernels' row tile (16 or 32;
+    0 = the launcher's choice)."""
+    if (x0.dim() != 2 or U.dim() != 3 or V.dim() != 3 or b.dim() != 2
+            or V.shape[1] < 1
+            or U.shape != (b.shape[0], b.shape[1], V.shape[1])
+            or V.shape != (b.shape[0], V.shape[1], b.shape[1])
+            or x0.shape[1] not in (b.shape[1], (b.shape[1] + 31) // 32 * 32)
+            or (w_out is None) != (b_out is None)
+            or (partial is not None and w_out is None)):
+        raise ValueError("cross_network_lr takes x0 [M, d or ceil32(d)], "
+                         "U [L, d, r], V [L, r, d], b [L, d], w_out [d] "
+                         "with b_out [1]")
+    if (_CROSS_LR and _cross_lr_fits(x0, U, V, b, w_out, b_out, partial)
+            and require_hip() is not None):
+        return _CrossLRFn.apply(x0, U, V, b, w_out, b_out, partial,
+                                torch.is_grad_enabled(), bm)
+    return _cross_lr_torch(x0, U, V, b, w_out, b_out, partial)
+
+
 # ----------------------------------------------------------------- fused loss
 
 class _FusedBCEFn(torch.autograd.Function):

@@ -25,6 +25,7 @@ ext = CUDAExtension(
         "openembedding_amd/ops/csrc/cin.hip",
         "openembedding_amd/ops/csrc/dlrm.hip",
         "openembedding_amd/ops/csrc/cross.hip",
+        "openembedding_amd/ops/csrc/cross_lr.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3"],
