@@ -35,6 +35,20 @@ _HEAD_ROWS = _HEAD_ROWS_ENV != "0"
 _HEAD_ROWS_FWD = _HEAD_ROWS_ENV not in ("0", "bwd")
 _HEAD_ROWS_BWD = _HEAD_ROWS_ENV not in ("0", "fwd")
 
+# Fused dense-parameter tail (docs/kernels.md "Dense tail"): the fused MLP's
+# backward leaves its wgrad / bias sums in the fp32 scratches and the flat
+# optimizer's step folds them, updates and writes the weight images in one
+# launch. OEAMD_DENSE_TAIL=0 keeps the two finishers, the two flat optimizer
+# launches and the forward's pack, in the same build. Read once at import.
+_DENSE_TAIL = os.environ.get("OEAMD_DENSE_TAIL", "1") != "0"
+
+
+def _tail_owner(bufs):
+    """The flat optimizer this MLP's buffers are registered with, if it is
+    still alive."""
+    ref = bufs.get("tail_opt")
+    return ref() if ref is not None else None
+
 
 class _FusedCTRHeadFn(torch.autograd.Function):
     """Fused interaction head (ops/csrc/ctrhead.hip): one kernel assembles
@@ -108,14 +122,25 @@ class _FusedMLP3Fn(torch.autograd.Function):
         # needs_input_grad reflects requires_grad alone and grad mode is
         # always off in here, so the caller's grad mode comes in through
         # bufs["grad_mode"] (_dnn_out sets it; absent = assume enabled).
-        srcs = [w1, w2, w3]
-        dsts = [bufs["w1p"], bufs["w2p"], bufs["w3p"]]
-        trans = [False, False, False]
-        if any(ctx.needs_input_grad) and bufs.get("grad_mode", True):
-            srcs += [w3, w2, w1]
-            dsts += [bufs["w3tp"], bufs["w2tp"], bufs["w1tp"]]
-            trans += [True, True, True]
-        ext.mlp3_pack_frag([w.contiguous() for w in srcs], dsts, trans)
+        # When the last optimizer step ran the fused dense tail, it wrote
+        # the forward images itself, and the transposed ones into a set of
+        # its own (w1tq..w3tq: the w*tp buffers stay what the last packing
+        # forward wrote), and left a stamp of the weights they stand for;
+        # while the stamp matches, nothing is packed here and the backward
+        # reads the tail's transposed set.
+        stamp = bufs.get("tail_stamp")
+        owner = _tail_owner(bufs) if stamp is not None else None
+        ctx.tail_images = (owner is not None
+                           and stamp == owner.mlp3_stamp(w1, w2, w3))
+        if not ctx.tail_images:
+            srcs = [w1, w2, w3]
+            dsts = [bufs["w1p"], bufs["w2p"], bufs["w3p"]]
+            trans = [False, False, False]
+            if any(ctx.needs_input_grad) and bufs.get("grad_mode", True):
+                srcs += [w3, w2, w1]
+                dsts += [bufs["w3tp"], bufs["w2tp"], bufs["w1tp"]]
+                trans += [True, True, True]
+            ext.mlp3_pack_frag([w.contiguous() for w in srcs], dsts, trans)
         w4f = w4.reshape(-1).contiguous()
         # partial (the head's first-order+FM+dense logits) folds into the
         # final-dot epilogue, replacing the `partial + dnn` add kernel
@@ -155,9 +180,11 @@ class _FusedMLP3Fn(torch.autograd.Function):
                 bscratch = torch.zeros(4 * H0 + 1, dtype=torch.float32,
                                        device=a1.device)
                 bufs["bscratch"] = bscratch
+        tkeys = (("w3tq", "w2tq", "w1tq") if ctx.tail_images
+                 else ("w3tp", "w2tp", "w1tp"))
         dx0, dz1, dz2, dz3 = ext.mlp3_bwd(
             dout.contiguous(), a1, a2, a3, w4f,
-            bufs["w3tp"], bufs["w2tp"], bufs["w1tp"], bscratch, frag=True)
+            *(bufs[k] for k in tkeys), bscratch, frag=True)
         # bias grads as GEMVs (fallback paths): torch's column-sum of
         # row-major bf16 ran ~16 us each (reduce_kernel); ones@dz is a
         # hipBLASLt GEMV. The default path below does them in the fused
@@ -189,6 +216,18 @@ class _FusedMLP3Fn(torch.autograd.Function):
             # head sums already rode the dgrad kernel above — the separate
             # bias pass disappears entirely (only its finisher runs)
             bias_in_wgrad = wgrad_fused and bias_fused
+            # dense tail: the sums stay in the scratches and the optimizer
+            # that owns these grads folds them in its step. Sums still
+            # pending here mean a second backward before the step: they are
+            # folded first, so the grads accumulate in bf16 as ever.
+            owner = _tail_owner(bufs) if _DENSE_TAIL else None
+            defer = (bias_in_wgrad and owner is not None
+                     and owner.defers_mlp3(bufs))
+            if bufs.get("tail_pending"):
+                ext.mlp3_finish(bufs["wscratch"], bufs["bscratch"], K0p,
+                                [w1g, w2g, w3g],
+                                [b1g, b2g, b3g, w4g.reshape(-1), b4g])
+                bufs["tail_pending"] = False
             if wgrad_fused:
                 # K0p <= 512: at the dim9 shapes the fused kernel beats the
                 # hipBLASLt trio (12.29 -> 12.62M); at dim64 (K0p 1696)
@@ -205,7 +244,8 @@ class _FusedMLP3Fn(torch.autograd.Function):
                     bufs["wscratch"] = scratch
                 ext.mlp3_wgrad(dz1, dz2, dz3, x0, a1, a2, scratch,
                                w1g, w2g, w3g,
-                               bscratch if bias_in_wgrad else None)
+                               bscratch if bias_in_wgrad else None,
+                               finish=not defer)
             else:
                 w1g.addmm_(dz1.t(), x0[:, :K0])
                 w2g.addmm_(dz2.t(), a1)
@@ -221,7 +261,9 @@ class _FusedMLP3Fn(torch.autograd.Function):
                 ext.mlp3_bias_bwd(dout.contiguous(), dz1, dz2, dz3, a3,
                                   bscratch, b1g, b2g, b3g,
                                   w4g.reshape(-1), b4g,
-                                  not bias_in_wgrad, False)
+                                  not bias_in_wgrad, False,
+                                  finish=not defer)
+                bufs["tail_pending"] = defer
             else:
                 d, ones = _d(), _ones()
                 w4g.addmm_(d, a3)
@@ -290,6 +332,17 @@ class _DNNHead(nn.Module):
                                "w3p": z(H, Hp), "w3tp": z(H, Hp),
                                "w2tp": z(H, Hp), "w1tp": z(K0p, Hp)}
             self._w1pad["grad_mode"] = torch.is_grad_enabled()
+            # dense tail: once a flat optimizer has rebased the weights,
+            # register the MLP and these buffers with it (again if the
+            # optimizer or the buffers were rebuilt)
+            opt_ref = getattr(l1.weight, "_oe_flat_opt", None)
+            if opt_ref is not None and (
+                    self._w1pad.get("tail_opt") is not opt_ref):
+                opt = opt_ref()
+                if opt is not None:
+                    opt.register_mlp3(
+                        (l1.weight, l1.bias, l2.weight, l2.bias, l3.weight,
+                         l3.bias, l4.weight, l4.bias), self._w1pad)
             return _FusedMLP3Fn.apply(
                 deep_in, partial, l1.weight, l1.bias, l2.weight, l2.bias,
                 l3.weight, l3.bias, l4.weight, l4.bias, self._w1pad)

@@ -17,6 +17,8 @@
 #include <tuple>
 #include <vector>
 
+#include "dense_tail.h"
+
 // torch instantiates data_ptr<int64_t> (long on LP64); the kernel TU uses
 // long long — same width, C linkage, so the pointer casts below are safe.
 typedef unsigned long long u64;
@@ -141,10 +143,14 @@ void emb_cross_lr_bwd(const void*, const void*, const void*, const void*,
                       hipStream_t_);
 void emb_mlp3_bias_bwd(const float*, const void*, const void*, const void*,
                        const void*, long, long, float*, void*, void*, void*,
-                       void*, void*, int, int, hipStream_t_);
+                       void*, void*, int, int, int, hipStream_t_);
 void emb_mlp3_wgrad(const void*, const void*, const void*, const void*,
                     const void*, const void*, long, long, long, long,
-                    float*, void*, void*, void*, float*, long, hipStream_t_);
+                    float*, void*, void*, void*, float*, long, int,
+                    hipStream_t_);
+void emb_mlp3_finish(float*, float*, long, long, long, void*, void*, void*,
+                     void*, void*, void*, void*, void*, hipStream_t_);
+void emb_dense_tail(int, const DenseTailArgs*, hipStream_t_);
 void emb_mlp3_pack(const void*, void*, long, long, long, long, int,
                    const void*, void*, long, long, long, long, int,
                    const void*, void*, long, long, long, long, int,
@@ -2019,7 +2025,7 @@ void mlp3_bias_bwd(torch::Tensor dout, torch::Tensor dz1, torch::Tensor dz2,
                    torch::Tensor dz3, torch::Tensor a3, torch::Tensor scratch,
                    torch::Tensor db1, torch::Tensor db2, torch::Tensor db3,
                    torch::Tensor dw4, torch::Tensor db4, bool with_dz,
-                   bool with_head) {
+                   bool with_head, bool finish) {
     CHECK_GPU(dout); CHECK_CONT(dout); CHECK_CONT(dz1); CHECK_CONT(dz2);
     CHECK_CONT(dz3); CHECK_CONT(a3); CHECK_CONT(scratch);
     long M = dz1.size(0), H = dz1.size(1);
@@ -2039,7 +2045,7 @@ void mlp3_bias_bwd(torch::Tensor dout, torch::Tensor dz1, torch::Tensor dz2,
                       scratch.data_ptr<float>(),
                       db1.data_ptr(), db2.data_ptr(), db3.data_ptr(),
                       dw4.data_ptr(), db4.data_ptr(), with_dz ? 1 : 0,
-                      with_head ? 1 : 0, cur_stream());
+                      with_head ? 1 : 0, finish ? 1 : 0, cur_stream());
 }
 
 // ---- DLRM pairwise dot interaction (dlrm.hip) ---------------------------
@@ -2465,7 +2471,10 @@ std::tuple<torch::Tensor, torch::Tensor> cin_dx(
 void mlp3_wgrad(torch::Tensor dz1, torch::Tensor dz2, torch::Tensor dz3,
                 torch::Tensor x0, torch::Tensor a1, torch::Tensor a2,
                 torch::Tensor scratch, torch::Tensor dw1, torch::Tensor dw2,
-                torch::Tensor dw3, OptTensor bias_scratch, long m_split) {
+                torch::Tensor dw3, OptTensor bias_scratch, long m_split,
+                bool finish) {
+    // finish=false leaves the sums in the scratches for dense_tail (or
+    // mlp3_finish); the grads are then neither read nor written here
     // bias_scratch ([4H+1] fp32, the bias pass scratch): when given, the
     // kernel also accumulates the three dz column sums (bias grads) from
     // its LDS-staged tiles into segments 0/H/2H
@@ -2502,7 +2511,175 @@ void mlp3_wgrad(torch::Tensor dz1, torch::Tensor dz2, torch::Tensor dz3,
                    x0.data_ptr(), a1.data_ptr(), a2.data_ptr(), M, H, K0p,
                    K0, scratch.data_ptr<float>(), dw1.data_ptr(),
                    dw2.data_ptr(), dw3.data_ptr(), bptr, m_split,
-                   cur_stream());
+                   finish ? 1 : 0, cur_stream());
+}
+
+// ---- fused MLP: deferred finishers and the dense tail -------------------
+
+namespace {
+bool aligned16(const torch::Tensor& t) {
+    return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0;
+}
+
+// shapes of the fused MLP's eight bf16 grads or parameters; returns H
+long check_mlp3_params(const std::vector<torch::Tensor>& ws,
+                       const std::vector<torch::Tensor>& smalls,
+                       const torch::Tensor& like, const char* what) {
+    TORCH_CHECK(ws.size() == 3 && smalls.size() == 5, what,
+                ": wants [w1, w2, w3] and [b1, b2, b3, w4, b4]");
+    const long H = ws[0].size(0);
+    for (const torch::Tensor& t : ws)
+        TORCH_CHECK(t.dim() == 2 && t.size(0) == H, what, ": weight shape");
+    TORCH_CHECK(ws[1].size(1) == H && ws[2].size(1) == H, what,
+                ": w2, w3 must be [H, H]");
+    for (size_t i = 0; i < 5; i++)
+        TORCH_CHECK(smalls[i].numel() == (i < 4 ? H : 1), what,
+                    ": b1, b2, b3, w4 hold H elements, b4 one");
+    for (const std::vector<torch::Tensor>* v : {&ws, &smalls})
+        for (const torch::Tensor& t : *v)
+            TORCH_CHECK(t.is_cuda() && t.device() == like.device()
+                        && t.dtype() == torch::kBFloat16
+                        && t.is_contiguous(), what,
+                        ": bf16 contiguous tensors on one device");
+    return H;
+}
+}  // namespace
+
+void mlp3_finish(torch::Tensor wscratch, torch::Tensor bscratch, long K0p,
+                 std::vector<torch::Tensor> dws,
+                 std::vector<torch::Tensor> dsmalls) {
+    // k_mlp3_wgrad_finish + k_mlp3_bias_finish on sums that a backward with
+    // finish=false left in the scratches
+    CHECK_GPU(wscratch); CHECK_CONT(wscratch); CHECK_CONT(bscratch);
+    const long H = check_mlp3_params(dws, dsmalls, wscratch, "mlp3_finish");
+    const long K0 = dws[0].size(1);
+    TORCH_CHECK(wscratch.dtype() == torch::kFloat32
+                && bscratch.dtype() == torch::kFloat32
+                && bscratch.device() == wscratch.device()
+                && K0 <= K0p && wscratch.numel() >= H * K0p + 2 * H * H
+                && bscratch.numel() >= 4 * H + 1, "mlp3_finish scratches");
+    const c10::cuda::CUDAGuard guard(wscratch.device());
+    emb_mlp3_finish(wscratch.data_ptr<float>(), bscratch.data_ptr<float>(),
+                    H, K0p, K0, dws[0].data_ptr(), dws[1].data_ptr(),
+                    dws[2].data_ptr(), dsmalls[0].data_ptr(),
+                    dsmalls[1].data_ptr(), dsmalls[2].data_ptr(),
+                    dsmalls[3].data_ptr(), dsmalls[4].data_ptr(),
+                    cur_stream());
+}
+
+void dense_tail(int64_t opt, torch::Tensor flat, torch::Tensor master,
+                OptTensor s1, OptTensor s2, torch::Tensor flat_grad,
+                std::vector<torch::Tensor> ws,
+                std::vector<torch::Tensor> smalls, torch::Tensor wscratch,
+                torch::Tensor bscratch, std::vector<torch::Tensor> imgs,
+                std::vector<torch::Tensor> timgs, OptTensor p32,
+                OptTensor s1_32, OptTensor s2_32, OptTensor g32,
+                OptTensor sc, double lr, double c0, double c1, double c2) {
+    // One launch for the whole dense-parameter tail of a fused-MLP model
+    // (mlp.hip: k_dense_tail). ws / smalls are the parameters themselves,
+    // views into `flat`, which must consist of exactly these eight; their
+    // grads sit at the same offsets of flat_grad. imgs = [w1p, w2p, w3p],
+    // timgs = [w1tp, w2tp, w3tp] (pads already written by mlp3_pack_frag).
+    CHECK_GPU(flat); CHECK_CONT(flat); CHECK_CONT(master);
+    CHECK_CONT(flat_grad); CHECK_CONT(wscratch); CHECK_CONT(bscratch);
+    TORCH_CHECK(opt >= 0 && opt <= 2, "dense_tail: opt");
+    const long n = flat.numel();
+    auto f32n = [&](const torch::Tensor& t, long want) {
+        return t.is_cuda() && t.device() == flat.device()
+            && t.dtype() == torch::kFloat32 && t.is_contiguous()
+            && t.numel() == want;
+    };
+    TORCH_CHECK(flat.dtype() == torch::kBFloat16
+                && flat_grad.dtype() == torch::kBFloat16
+                && flat_grad.numel() == n
+                && flat_grad.device() == flat.device()
+                && f32n(master, n) && n < (1L << 31),
+                "dense_tail: flat bf16 group");
+    TORCH_CHECK((!s1.has_value() || (f32n(*s1, n) && aligned16(*s1)))
+                && (!s2.has_value() || (f32n(*s2, n) && aligned16(*s2))),
+                "dense_tail: optimizer state");
+    // whole pieces move as 16-byte vectors
+    TORCH_CHECK(aligned16(flat) && aligned16(flat_grad) && aligned16(master),
+                "dense_tail: flat buffers must be 16-byte aligned");
+    // state the optimizer reads must be there (flat_opt.h)
+    TORCH_CHECK(s1.has_value() || (opt == 0 && c0 == 0.0),
+                "dense_tail: s1 missing");
+    TORCH_CHECK(opt != 2 || (s2.has_value() && sc.has_value()),
+                "dense_tail: adam wants s2 and the step scalars");
+    if (sc.has_value())
+        TORCH_CHECK(f32n(*sc, sc->numel()) && sc->numel() >= 3,
+                    "dense_tail: step scalars");
+    const long H = check_mlp3_params(ws, smalls, flat, "dense_tail");
+    TORCH_CHECK(imgs.size() == 3 && timgs.size() == 3,
+                "dense_tail: three images and three transposed images");
+    TORCH_CHECK(H % 16 == 0, "dense_tail: H must be x16");
+    DenseTailArgs a = {};
+    const char* base = static_cast<const char*>(flat.data_ptr());
+    auto off_of = [&](const torch::Tensor& t) {
+        const long d = static_cast<const char*>(t.data_ptr()) - base;
+        TORCH_CHECK(d >= 0 && d % 2 == 0 && d / 2 + t.numel() <= n,
+                    "dense_tail: parameter outside the flat group");
+        return (int)(d / 2);
+    };
+    long covered = 0, woff = 0;
+    for (int l = 0; l < 3; l++) {
+        const torch::Tensor &w = ws[l], &img = imgs[l], &timg = timgs[l];
+        const long cols = w.size(1);
+        for (const torch::Tensor* t : {&img, &timg})
+            TORCH_CHECK(t->is_cuda() && t->device() == flat.device()
+                        && t->dtype() == torch::kBFloat16 && t->dim() == 2
+                        && t->is_contiguous() && aligned16(*t)
+                        && t->size(0) % 16 == 0 && t->size(1) % 32 == 0,
+                        "dense_tail: images are bf16 [x16, x32], aligned");
+        TORCH_CHECK(img.size(0) == H && img.size(1) >= cols
+                    && timg.size(0) >= cols && timg.size(1) >= H,
+                    "dense_tail: image shapes");
+        // scratch row stride: K0p (the image's Kp) for w1, H for w2, w3
+        const long sld = l == 0 ? img.size(1) : H;
+        TORCH_CHECK(cols <= sld && sld % 8 == 0, "dense_tail: scratch rows");
+        a.m[l] = DenseTailMat{wscratch.data_ptr<float>() + woff,
+                              img.data_ptr(), timg.data_ptr(), off_of(w),
+                              (int)H, (int)cols, (int)sld,
+                              (int)(img.size(1) / 32),
+                              (int)(timg.size(1) / 32)};
+        woff += H * sld;
+        covered += w.numel();
+    }
+    TORCH_CHECK(f32n(wscratch, wscratch.numel()) && wscratch.numel() >= woff
+                && aligned16(wscratch) && woff < (1L << 31)
+                && f32n(bscratch, bscratch.numel())
+                && bscratch.numel() >= 4 * H + 1, "dense_tail: scratches");
+    a.so0 = off_of(smalls[0]); a.so1 = off_of(smalls[1]);
+    a.so2 = off_of(smalls[2]); a.so3 = off_of(smalls[3]);
+    a.so4 = off_of(smalls[4]);
+    covered += 4 * H + 1;
+    TORCH_CHECK(covered == n, "dense_tail: the flat bf16 group must consist "
+                "of exactly the MLP's eight parameters");
+    a.H = (int)H;
+    a.bscratch = bscratch.data_ptr<float>();
+    a.master = master.data_ptr<float>();
+    a.s1 = s1.has_value() ? s1->data_ptr<float>() : nullptr;
+    a.s2 = s2.has_value() ? s2->data_ptr<float>() : nullptr;
+    a.grad = flat_grad.data_ptr();
+    a.flat = flat.data_ptr();
+    if (p32.has_value()) {
+        const long n32 = p32->numel();
+        TORCH_CHECK(g32.has_value() && f32n(*p32, n32) && f32n(*g32, n32)
+                    && (!s1_32.has_value() || f32n(*s1_32, n32))
+                    && (!s2_32.has_value() || f32n(*s2_32, n32))
+                    && s1_32.has_value() == s1.has_value()
+                    && s2_32.has_value() == s2.has_value()
+                    && n32 < (1L << 30), "dense_tail: fp32 group");
+        a.p32 = p32->data_ptr<float>();
+        a.g32 = g32->data_ptr<float>();
+        a.s1_32 = s1_32.has_value() ? s1_32->data_ptr<float>() : nullptr;
+        a.s2_32 = s2_32.has_value() ? s2_32->data_ptr<float>() : nullptr;
+        a.n32 = (int)n32;
+    }
+    a.sc = sc.has_value() ? sc->data_ptr<float>() : nullptr;
+    a.lr = (float)lr; a.c0 = (float)c0; a.c1 = (float)c1; a.c2 = (float)c2;
+    const c10::cuda::CUDAGuard guard(flat.device());
+    emb_dense_tail((int)opt, &a, cur_stream());
 }
 
 void mlp3_pack(torch::Tensor s1, torch::Tensor d1, bool t1,
@@ -2914,9 +3091,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("scratch"), pybind11::arg("dw1"),
           pybind11::arg("dw2"), pybind11::arg("dw3"),
           pybind11::arg("bias_scratch") = pybind11::none(),
-          pybind11::arg("m_split") = 0,
+          pybind11::arg("m_split") = 0, pybind11::arg("finish") = true,
           "all three MLP weight grads in one MFMA launch (+= into bf16 "
           "grads via fp32 scratch)");
+    m.def("mlp3_finish", &mlp3_finish,
+          "fold deferred wgrad / bias sums into the bf16 grads (both "
+          "finishers, nothing else)",
+          pybind11::arg("wscratch"), pybind11::arg("bscratch"),
+          pybind11::arg("K0p"), pybind11::arg("dws"),
+          pybind11::arg("dsmalls"));
+    m.def("dense_tail", &dense_tail,
+          "fused dense-parameter tail: deferred wgrad / bias fold, flat "
+          "optimizer (both dtype groups) and the six weight images in one "
+          "launch",
+          pybind11::arg("opt"), pybind11::arg("flat"),
+          pybind11::arg("master"), pybind11::arg("s1"), pybind11::arg("s2"),
+          pybind11::arg("flat_grad"), pybind11::arg("ws"),
+          pybind11::arg("smalls"), pybind11::arg("wscratch"),
+          pybind11::arg("bscratch"), pybind11::arg("imgs"),
+          pybind11::arg("timgs"), pybind11::arg("p32"),
+          pybind11::arg("s1_32"), pybind11::arg("s2_32"),
+          pybind11::arg("g32"), pybind11::arg("sc"), pybind11::arg("lr"),
+          pybind11::arg("c0"), pybind11::arg("c1"), pybind11::arg("c2"));
     m.def("mlp3_bias_bwd", &mlp3_bias_bwd,
           "MLP bias grads + head wgrad in one pass over the dz mirrors "
           "(with_dz=false when the fused wgrad carried the dz sums)",
@@ -2925,7 +3121,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("scratch"), pybind11::arg("db1"),
           pybind11::arg("db2"), pybind11::arg("db3"), pybind11::arg("dw4"),
           pybind11::arg("db4"), pybind11::arg("with_dz") = true,
-          pybind11::arg("with_head") = true);
+          pybind11::arg("with_head") = true, pybind11::arg("finish") = true);
     m.def("dot_interact_fwd", &dot_interact_fwd,
           "DLRM interaction fwd: [x | strict lower triangle of the Gram "
           "matrix of (x, e rows)] on MFMA, one launch",

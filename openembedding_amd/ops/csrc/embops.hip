@@ -2333,7 +2333,9 @@ __global__ void k_flat_adagrad_bf16(float* __restrict__ master,
 // DEVICE scalars prepared by k_flat_step_scalars so a hipGraph-captured
 // step keeps correcting (a host-side 1-beta^t would freeze at capture).
 
-enum { FLAT_SGD = 0, FLAT_ADAGRAD = 1, FLAT_ADAM = 2 };
+// The per-element update (flat_opt_step) is shared with the fused dense
+// tail in mlp.hip.
+#include "flat_opt.h"
 
 __global__ void k_flat_step_scalars(float* __restrict__ sc, float b1,
                                     float b2) {
@@ -2342,33 +2344,6 @@ __global__ void k_flat_step_scalars(float* __restrict__ sc, float b1,
     sc[0] = t;
     sc[1] = 1.0f - powf(b1, t);
     sc[2] = 1.0f - powf(b2, t);
-}
-
-template <int OPT>
-__device__ __forceinline__ float flat_opt_step(
-        float w, float gi, float* __restrict__ s1, float* __restrict__ s2,
-        long i, const float* __restrict__ sc, float lr, float c0, float c1,
-        float c2) {
-    if (OPT == FLAT_ADAGRAD) {
-        float a = s1[i] + gi * gi;
-        s1[i] = a;
-        return w - lr * gi / (sqrtf(a) + c0);
-    }
-    if (OPT == FLAT_SGD) {
-        if (c0 == 0.0f) return w - lr * gi;     // plain
-        float b = c0 * s1[i] + gi;              // momentum, dampening 0
-        s1[i] = b;
-        float d = (c1 != 0.0f) ? gi + c0 * b : b;   // c1 = nesterov
-        return w - lr * d;
-    }
-    // FLAT_ADAM: c0=beta1, c1=beta2, c2=eps; sc[1]=1-b1^t, sc[2]=1-b2^t
-    float m = c0 * s1[i] + (1.0f - c0) * gi;
-    float v = c1 * s2[i] + (1.0f - c1) * gi * gi;
-    s1[i] = m;
-    s2[i] = v;
-    float mh = m / sc[1];
-    float vh = v / sc[2];
-    return w - lr * mh / (sqrtf(vh) + c2);
 }
 
 // Both variants zero the grad element after consuming it: the next

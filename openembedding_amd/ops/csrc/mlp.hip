@@ -24,6 +24,9 @@
 #include <hip/hip_bf16.h>
 #include <cstdint>
 
+#include "dense_tail.h"
+#include "flat_opt.h"
+
 typedef __hip_bfloat16 mbf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -551,7 +554,8 @@ extern "C" void emb_mlp3_bias_bwd(const float* dout, const void* dz1,
                                   long M, long H, float* scratch,
                                   void* db1, void* db2, void* db3,
                                   void* dw4, void* db4, int with_dz,
-                                  int with_head, hipStream_t stream) {
+                                  int with_head, int finish,
+                                  hipStream_t stream) {
     if (M == 0) return;
     const long rows_per_blk = 32;
     int ga = (int)((M + rows_per_blk - 1) / rows_per_blk);
@@ -560,6 +564,9 @@ extern "C" void emb_mlp3_bias_bwd(const float* dout, const void* dz1,
             dout, (const mbf16*)dz1, (const mbf16*)dz2, (const mbf16*)dz3,
             (const mbf16*)a3, M, H, rows_per_blk, scratch, with_dz,
             with_head);
+    // finish == 0: the scratch keeps the sums for k_dense_tail, which folds
+    // them into the grads on its way through the optimizer
+    if (!finish) return;
     int gb = (int)((4 * H + 1 + 255) / 256);
     k_mlp3_bias_finish<<<gb, 256, 0, stream>>>(
         scratch, H, (mbf16*)db1, (mbf16*)db2, (mbf16*)db3, (mbf16*)dw4,
@@ -939,7 +946,7 @@ extern "C" void emb_mlp3_wgrad(const void* dz1, const void* dz2,
                                long M, long H, long K0p, long K0,
                                float* scratch,
                                void* dw1, void* dw2, void* dw3,
-                               float* bias_out, long m_split,
+                               float* bias_out, long m_split, int finish,
                                hipStream_t stream) {
     if (!M) return;
     // m_split: each split adds a full 64x64 fp32 tile with float atomics
@@ -968,9 +975,25 @@ extern "C" void emb_mlp3_wgrad(const void* dz1, const void* dz2,
         (const mbf16*)dz1, (const mbf16*)dz2, (const mbf16*)dz3,
         (const mbf16*)x0, (const mbf16*)a1, (const mbf16*)a2, M, H, K0p,
         t1, tk, th, scratch, m_split, bias_out);
+    if (!finish) return;    // k_dense_tail folds the scratch (see there)
     long total = H * K0p + 2 * H * H;
     k_mlp3_wgrad_finish<<<(int)((total + 255) / 256), 256, 0, stream>>>(
         scratch, H, K0p, K0, (mbf16*)dw1, (mbf16*)dw2, (mbf16*)dw3);
+}
+
+// Both finishers alone, for sums that a deferred backward (finish == 0) left
+// in the scratches and that no k_dense_tail will consume: a second backward
+// before the optimizer step folds the first one's sums in bf16 first.
+extern "C" void emb_mlp3_finish(float* wscratch, float* bscratch, long H,
+                                long K0p, long K0, void* dw1, void* dw2,
+                                void* dw3, void* db1, void* db2, void* db3,
+                                void* dw4, void* db4, hipStream_t stream) {
+    long total = H * K0p + 2 * H * H;
+    k_mlp3_wgrad_finish<<<(int)((total + 255) / 256), 256, 0, stream>>>(
+        wscratch, H, K0p, K0, (mbf16*)dw1, (mbf16*)dw2, (mbf16*)dw3);
+    k_mlp3_bias_finish<<<(int)((4 * H + 1 + 255) / 256), 256, 0, stream>>>(
+        bscratch, H, (mbf16*)db1, (mbf16*)db2, (mbf16*)db3, (mbf16*)dw4,
+        (mbf16*)db4);
 }
 
 // ---- fused weight repack ----------------------------------------------
@@ -1128,4 +1151,209 @@ extern "C" void emb_mlp3_pack_frag(int n, const void* const* srcs,
     dim3 grid((unsigned)mx, (unsigned)n);
     k_mlp3_pack_frag<<<grid, threads, 0, stream>>>(p[0], p[1], p[2], p[3],
                                                    p[4], p[5]);
+}
+
+// ---- fused dense-parameter tail ---------------------------------------
+// After a backward whose finishers were deferred (finish == 0 above), ONE
+// launch does what five did one after the other over the same ~420 k dense
+// parameters: k_mlp3_wgrad_finish, k_mlp3_bias_finish, k_flat_opt_f32,
+// k_flat_opt_bf16 and the next forward's k_mlp3_pack_frag. Per element, in
+// the order of roundings of those five:
+//     g = (bf16)((float)grad[i] + scratch[j]);  scratch[j] = 0
+//     m = flat_opt_step<OPT>(master[i], (float)g, ...)
+//     master[i] = m;  flat[i] = (bf16)m;  grad[i] = 0
+//     forward image and transposed image <- (bf16)m
+//
+// The grid walks the FORWARD images in destination order, like
+// k_mlp3_pack_frag: blockIdx.z = 0..2 selects w1, w2, w3, blockIdx.x a
+// 16-row chunk, blockIdx.y a group of 4 k-steps, and thread t of the 256
+// owns one 16-byte piece = 8 consecutive k of one row n. It writes the
+// piece with one 16-byte store and the same 8 values into the transposed
+// image with 2-byte stores (they ride L2, as pack_frag's transposed reads
+// did). Every scratch entry of the row is zeroed, w1's pad columns
+// (col >= cols, no parameter behind them) included. Image pads are never
+// written: a full mlp3_pack_frag wrote them when the buffers were made, and
+// a piece that straddles the last valid column stores the zeros it holds.
+// blockIdx.z = 3 (its blockIdx.y = 0 blocks) covers b1..b3, w4, b4 from
+// bscratch and then the flat fp32 group, elementwise. All indices are
+// 32-bit, no division.
+template <int OPT>
+__global__ void __launch_bounds__(256) k_dense_tail(DenseTailArgs a) {
+    float* __restrict__ master = a.master;
+    mbf16* __restrict__ grad = reinterpret_cast<mbf16*>(a.grad);
+    mbf16* __restrict__ flat = reinterpret_cast<mbf16*>(a.flat);
+    const int z = (int)blockIdx.z;
+    if (z == 3) {
+        if (blockIdx.y) return;
+        const int H = a.H, nsm = 4 * H + 1, total = nsm + a.n32;
+        for (int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+             idx < total; idx += (int)(gridDim.x * blockDim.x)) {
+            if (idx < nsm) {
+                float v = a.bscratch[idx];
+                a.bscratch[idx] = 0.f;
+                const int i = idx < H     ? a.so0 + idx
+                            : idx < 2 * H ? a.so1 + (idx - H)
+                            : idx < 3 * H ? a.so2 + (idx - 2 * H)
+                            : idx < 4 * H ? a.so3 + (idx - 3 * H)
+                            :               a.so4;
+                mbf16 g = (mbf16)((float)grad[i] + v);
+                float m = flat_opt_step<OPT>(master[i], (float)g, a.s1, a.s2,
+                                             i, a.sc, a.lr, a.c0, a.c1, a.c2);
+                master[i] = m;
+                flat[i] = (mbf16)m;
+                grad[i] = (mbf16)0.0f;
+            } else {
+                const int i = idx - nsm;    // k_flat_opt_f32's body
+                a.p32[i] = flat_opt_step<OPT>(a.p32[i], a.g32[i], a.s1_32,
+                                              a.s2_32, i, a.sc, a.lr, a.c0,
+                                              a.c1, a.c2);
+                a.g32[i] = 0.0f;
+            }
+        }
+        return;
+    }
+    const DenseTailMat p = z == 0 ? a.m[0] : z == 1 ? a.m[1] : a.m[2];
+    const int ch = (int)blockIdx.x;
+    const int t = (int)(blockIdx.y * blockDim.x + threadIdx.x);
+    if (ch * 16 >= p.rows || t >= p.ks * 64) return;
+    const int lane = t & 63;
+    const int n = ch * 16 + (lane & 15);
+    const int k = (t >> 6) * 32 + (lane >> 4) * 8;
+    if (k >= p.sld) return;         // image pad beyond the scratch row
+    f32x4* sp = reinterpret_cast<f32x4*>(
+        __builtin_assume_aligned(p.scratch + n * p.sld + k, 16));
+    const f32x4 v0 = sp[0], v1 = sp[1];
+    sp[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    sp[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (k >= p.cols) return;        // pad columns of the scratch only
+    const float sv[8] = {v0[0], v0[1], v0[2], v0[3],
+                         v1[0], v1[1], v1[2], v1[3]};
+    const int base = p.off + n * p.cols + k;
+    const int nv = p.cols - k;      // valid elements of the piece (>= 8: all)
+    // Every load of the piece is issued before the first use: one trip to
+    // memory per thread, not one per element (a load -> update -> store
+    // chain per element ran 16 us at the flagship shape). A piece that is
+    // whole and whose flat offset is a multiple of 8 (w2, w3) moves as
+    // 16-byte vectors; w1's rows (247 columns) go element by element.
+    constexpr bool ADAM = OPT == FLAT_ADAM;
+    const bool has1 = flat_opt_has_s1<OPT>(a.c0);
+    const bool vec = nv >= 8 && (base & 7) == 0;
+    const unsigned short* gbits =
+        reinterpret_cast<const unsigned short*>(a.grad);
+    float ms[8], x1[8], x2[8], gf[8];
+    if (vec) {
+        const f32x4* mp = reinterpret_cast<const f32x4*>(
+            __builtin_assume_aligned(master + base, 16));
+        const f32x4 m0 = mp[0], m1 = mp[1];
+        const u32x4 gv = *reinterpret_cast<const u32x4*>(
+            __builtin_assume_aligned(gbits + base, 16));
+        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, b0 = a0, b1 = a0;
+        if (has1) {
+            const f32x4* q = reinterpret_cast<const f32x4*>(
+                __builtin_assume_aligned(a.s1 + base, 16));
+            a0 = q[0]; a1 = q[1];
+        }
+        if (ADAM) {
+            const f32x4* q = reinterpret_cast<const f32x4*>(
+                __builtin_assume_aligned(a.s2 + base, 16));
+            b0 = q[0]; b1 = q[1];
+        }
+        #pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            ms[e] = m0[e]; ms[e + 4] = m1[e];
+            x1[e] = a0[e]; x1[e + 4] = a1[e];
+            x2[e] = b0[e]; x2[e + 4] = b1[e];
+        }
+        #pragma unroll
+        for (int e = 0; e < 8; ++e)
+            gf[e] = __uint_as_float(e & 1 ? gv[e >> 1] & 0xffff0000u
+                                          : gv[e >> 1] << 16);
+    } else {
+        #pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const bool ok = e < nv;
+            ms[e] = ok ? master[base + e] : 0.f;
+            gf[e] = ok ? bf16_bits_f32(gbits[base + e]) : 0.f;
+            x1[e] = ok && has1 ? a.s1[base + e] : 0.f;
+            x2[e] = ok && ADAM ? a.s2[base + e] : 0.f;
+        }
+    }
+    const float sc1 = ADAM ? a.sc[1] : 1.0f, sc2 = ADAM ? a.sc[2] : 1.0f;
+    unsigned w[8];
+    mbf16 wv[8];
+    #pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        mbf16 g = (mbf16)(gf[e] + sv[e]);
+        ms[e] = flat_opt_math<OPT>(ms[e], (float)g, x1[e], x2[e], sc1, sc2,
+                                   a.lr, a.c0, a.c1, a.c2);
+        wv[e] = (mbf16)ms[e];
+        w[e] = e < nv ? (unsigned)__builtin_bit_cast(unsigned short, wv[e])
+                      : 0u;
+    }
+    const u32x4 piece = {w[0] | w[1] << 16, w[2] | w[3] << 16,
+                         w[4] | w[5] << 16, w[6] | w[7] << 16};
+    if (vec) {
+        f32x4* mp = reinterpret_cast<f32x4*>(
+            __builtin_assume_aligned(master + base, 16));
+        mp[0] = f32x4{ms[0], ms[1], ms[2], ms[3]};
+        mp[1] = f32x4{ms[4], ms[5], ms[6], ms[7]};
+        if (has1) {
+            f32x4* q = reinterpret_cast<f32x4*>(
+                __builtin_assume_aligned(a.s1 + base, 16));
+            q[0] = f32x4{x1[0], x1[1], x1[2], x1[3]};
+            q[1] = f32x4{x1[4], x1[5], x1[6], x1[7]};
+        }
+        if (ADAM) {
+            f32x4* q = reinterpret_cast<f32x4*>(
+                __builtin_assume_aligned(a.s2 + base, 16));
+            q[0] = f32x4{x2[0], x2[1], x2[2], x2[3]};
+            q[1] = f32x4{x2[4], x2[5], x2[6], x2[7]};
+        }
+        *reinterpret_cast<u32x4*>(
+            __builtin_assume_aligned(flat + base, 16)) = piece;
+        *reinterpret_cast<u32x4*>(
+            __builtin_assume_aligned(grad + base, 16)) =
+            u32x4{0u, 0u, 0u, 0u};
+    } else {
+        #pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if (e < nv) {
+                master[base + e] = ms[e];
+                if (has1) a.s1[base + e] = x1[e];
+                if (ADAM) a.s2[base + e] = x2[e];
+                flat[base + e] = wv[e];
+                grad[base + e] = (mbf16)0.0f;
+            }
+        }
+    }
+    // transposed image: element (n', k') = (k + e, n)
+    mbf16* timg = reinterpret_cast<mbf16*>(p.timg)
+                + (n >> 5) * 512 + ((n & 31) >> 3) * 128 + (n & 7);
+    #pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int nt = k + e;
+        if (e < nv) timg[((nt >> 4) * p.tks) * 512 + (nt & 15) * 8] = wv[e];
+    }
+    u32x4* dst = reinterpret_cast<u32x4*>(p.img) + ch * p.ks * 64;
+    dst[t] = piece;
+}
+
+extern "C" void emb_dense_tail(int opt, const DenseTailArgs* a,
+                               hipStream_t stream) {
+    int nch = 0, ks = 0;
+    for (const DenseTailMat& m : a->m) {
+        if (m.rows / 16 > nch) nch = m.rows / 16;
+        if (m.ks > ks) ks = m.ks;
+    }
+    const int small = (4 * a->H + 1 + a->n32 + 255) / 256;
+    if (small > nch) nch = small;
+    dim3 grid((unsigned)nch, (unsigned)((ks + 3) / 4), 4);
+    switch (opt) {
+        case FLAT_SGD:
+            k_dense_tail<FLAT_SGD><<<grid, 256, 0, stream>>>(*a); break;
+        case FLAT_ADAGRAD:
+            k_dense_tail<FLAT_ADAGRAD><<<grid, 256, 0, stream>>>(*a); break;
+        case FLAT_ADAM:
+            k_dense_tail<FLAT_ADAM><<<grid, 256, 0, stream>>>(*a); break;
+    }
 }

@@ -636,6 +636,80 @@ class _FlatDenseOptimizer:
         if dev.type == "cuda":
             from ..ops import require_hip
             self._ext = require_hip()
+        # fused dense tail (docs/kernels.md "Dense tail"): a fused MLP finds
+        # the optimizer that rebased its parameters through this attribute
+        # and registers itself with register_mlp3
+        self._mlp3 = None
+        self._ref = weakref.ref(self)
+        for p in params:
+            p._oe_flat_opt = self._ref
+
+    # ---- fused dense tail ------------------------------------------------
+
+    def register_mlp3(self, params, bufs) -> bool:
+        """Registration hook of the fused dense tail. ``params`` are a fused
+        MLP's w1, b1, w2, b2, w3, b3, w4, b4 and ``bufs`` its buffer dict
+        (the six weight images, wscratch, bscratch). True when the flat bf16
+        group consists of exactly these eight: step() can then do the
+        deferred wgrad / bias fold, both optimizer groups and the weight
+        images in one launch (ext.dense_tail)."""
+        bufs["tail_opt"] = self._ref
+        bufs.pop("tail_stamp", None)
+        self._mlp3 = None
+        grp = next((g for g in self.groups
+                    if g["dtype"] == torch.bfloat16), None)
+        if (self._ext is None or grp is None or len(params) != 8
+                or any(p not in self._grad_views for p in params)
+                or sum(p.numel() for p in params) != grp["flat"].numel()
+                or any(p.dtype != torch.bfloat16 for p in params)):
+            return False
+        # the tail's own transposed images (pads zero, as a pack leaves
+        # them): bufs["w*tp"] stay what the last packing forward wrote
+        for l in ("w1", "w2", "w3"):
+            if l + "tq" not in bufs:
+                bufs[l + "tq"] = torch.zeros_like(bufs[l + "tp"])
+        self._mlp3 = {"params": tuple(params), "bufs": bufs, "group": grp}
+        return True
+
+    def defers_mlp3(self, bufs) -> bool:
+        """May this backward leave its wgrad / bias sums in the scratches
+        for step()? Only for the registered MLP, with every grad still the
+        flat buffer's view, and when no dense allreduce will read the flat
+        grads before the step."""
+        m = self._mlp3
+        return (m is not None and m["bufs"] is bufs
+                and all(p.grad is self._grad_views[p] for p in m["params"])
+                and not (comm.dist_ready() and dist.get_world_size() > 1))
+
+    @staticmethod
+    def mlp3_stamp(w1, w2, w3):
+        """What the weight images written by the dense tail stand for: any
+        in-place torch write moves a _version, a rebased or converted
+        parameter its data pointer."""
+        return tuple(w._version for w in (w1, w2, w3)) + tuple(
+            w.data_ptr() for w in (w1, w2, w3))
+
+    def _dense_tail(self, cfg):
+        m = self._mlp3
+        w1, b1, w2, b2, w3, b3, w4, b4 = m["params"]
+        bufs, g = m["bufs"], m["group"]
+        g32 = next((x for x in self.groups
+                    if x["dtype"] == torch.float32), None)
+        self._ext.dense_tail(
+            self.opt_id, g["flat"], g["master"], g["s1"], g["s2"],
+            g["flat_grad"], [w1, w2, w3], [b1, b2, b3, w4, b4],
+            bufs["wscratch"], bufs["bscratch"],
+            [bufs["w1p"], bufs["w2p"], bufs["w3p"]],
+            [bufs["w1tq"], bufs["w2tq"], bufs["w3tq"]],
+            g32["flat"] if g32 else None, g32["s1"] if g32 else None,
+            g32["s2"] if g32 else None, g32["flat_grad"] if g32 else None,
+            self.step_scalars, self.lr, *cfg)
+        bufs["tail_pending"] = False
+        bufs["tail_stamp"] = self.mlp3_stamp(w1, w2, w3)
+
+    def _drop_stamp(self):
+        if self._mlp3 is not None:
+            self._mlp3["bufs"].pop("tail_stamp", None)
 
     def zero_grad(self):
         for p, view in self._grad_views.items():
@@ -656,6 +730,12 @@ class _FlatDenseOptimizer:
             return
         for g in self.groups:
             g["flat_grad"].zero_()
+        m = self._mlp3
+        if m is not None and m["bufs"].get("tail_pending"):
+            # a deferred backward's sums are discarded with the grads
+            m["bufs"]["wscratch"].zero_()
+            m["bufs"]["bscratch"].zero_()
+            m["bufs"]["tail_pending"] = False
 
     def _check_bound(self):
         for p, view in self._grad_views.items():
@@ -680,6 +760,15 @@ class _FlatDenseOptimizer:
                 cfg = (self.eps, 0.0, 0.0)
             else:
                 cfg = (self.betas[0], self.betas[1], self.eps)
+            if (self._mlp3 is not None
+                    and self._mlp3["bufs"].get("tail_pending")):
+                # the backward left its sums in the scratches: one launch
+                # folds them, steps both groups and writes the images the
+                # next forward reads
+                self._dense_tail(cfg)
+                self._grads_zeroed = True
+                return
+            self._drop_stamp()      # the images go stale with this step
             for g in self.groups:
                 self._ext.flat_opt(self.opt_id, g["flat"], g["master"],
                                    g["s1"], g["s2"], g["flat_grad"],
@@ -727,6 +816,7 @@ class _FlatDenseOptimizer:
                                  else None)}
 
     def load_state_dict(self, sd):
+        self._drop_stamp()      # the flat copy below moves no p._version
         for g, s in zip(self.groups, sd["groups"]):
             g["flat"].copy_(s["flat"])
             for k in ("s1", "s2", "master"):
