@@ -2502,7 +2502,10 @@ __global__ void k_scatter_out(const float* __restrict__ rows_recv,
     out[e] = (pos >= 0) ? rows_recv[(u64)pos * dim + j] : 0.0f;
 }
 
-// split the owner-side reduced payload [u, dim+1] back into grads + counts
+// split the owner-side reduced payload [u, dim+1] back into grads + counts.
+// The count column is rounded to nearest (the torch route's .round()), not
+// by adding 0.5f: from 2^23 on that sum is a tie for every odd count and
+// rounds to the even neighbour, one too many.
 __global__ void k_split_payload(const float* __restrict__ g2c, long u,
                                 long dim, const int* __restrict__ u_dev,
                                 float* __restrict__ grads,
@@ -2513,7 +2516,7 @@ __global__ void k_split_payload(const float* __restrict__ g2c, long u,
     long r = e / dimp, j = e % dimp;
     if (u_dev && r >= *u_dev) return;
     if (j < dim) grads[(u64)r * dim + j] = g2c[e];
-    else counts[r] = (u64)(g2c[e] + 0.5f);
+    else counts[r] = (u64)rintf(g2c[e]);
 }
 
 // zero the garbage tail of a bounded (buffer + device-count) gradient

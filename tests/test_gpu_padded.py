@@ -124,11 +124,11 @@ def test_gather_split_payload_roundtrip():
     send_src[: n] = torch.arange(n, dtype=torch.int32, device=DEV)
     send_p = ext.gather_pad(ugrads, counts, send_src)
     assert send_p.shape == (world * cap, dim + 1)
-    torch.testing.assert_close(send_p[:n, :dim], ugrads)
+    assert torch.equal(send_p[:n, :dim], ugrads)
     assert torch.equal(send_p[:n, dim].long(), counts)
     assert float(send_p[n:].abs().sum()) == 0.0
     g2, c2 = ext.split_payload(send_p[:n].contiguous(), None)
-    torch.testing.assert_close(g2, ugrads)
+    assert torch.equal(g2, ugrads)
     assert torch.equal(c2, counts)
 
 
@@ -141,12 +141,12 @@ def test_scatter_out_kernel():
     pos_of = torch.tensor([5, -1, 9, 63], dtype=torch.int32, device=DEV)
     inverse = torch.tensor([0, 1, 2, 3, 0, 2], dtype=torch.int64, device=DEV)
     out = ext.scatter_out(rows, inverse, pos_of, inverse.numel())
-    torch.testing.assert_close(out[0], rows[5])
+    assert torch.equal(out[0], rows[5])
     assert float(out[1].abs().sum()) == 0.0
-    torch.testing.assert_close(out[2], rows[9])
-    torch.testing.assert_close(out[3], rows[63])
-    torch.testing.assert_close(out[4], rows[5])
-    torch.testing.assert_close(out[5], rows[9])
+    assert torch.equal(out[2], rows[9])
+    assert torch.equal(out[3], rows[63])
+    assert torch.equal(out[4], rows[5])
+    assert torch.equal(out[5], rows[9])
 
 
 def test_multi_pull_commit_merges_blocks():
