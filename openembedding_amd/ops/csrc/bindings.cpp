@@ -2116,33 +2116,57 @@ std::tuple<torch::Tensor, torch::Tensor> dot_interact_bwd(
 
 // ---- DCN-v2 cross network (cross.hip) -----------------------------------
 
-// Everything the kernels rely on, checked before a launch. The Python side
-// (ops.cross_network) tests the same limits and routes the rest to torch.
-// x0 [M, dp] bf16 with dp = ceil32(d), w an [L, dp, dp] stack of fragment-
-// major images (mlp3_pack_frag), b [L, d].
+// Everything the kernels rely on is checked before a launch; the Python side
+// (ops.cross_network, ops.cross_network_lr) tests the same limits and routes
+// the rest to torch. The argument helpers below serve both cross networks.
+
+// x0 [M, dp] bf16, the stacks of fragment-major weight images
+// (mlp3_pack_frag), b [L, d]: one device, bf16, their ranks (`shapes` names
+// them), contiguous. The shape limits, which need these, come next in the
+// caller, then cross_check_launch.
+static void cross_check_operands(const torch::Tensor& x0, at::TensorList imgs,
+                                 const torch::Tensor& b, const char* shapes,
+                                 const char* who) {
+    bool one_gpu = x0.is_cuda() && b.is_cuda() && b.device() == x0.device();
+    bool bf16 = x0.scalar_type() == torch::kBFloat16
+        && b.scalar_type() == torch::kBFloat16;
+    bool dims = x0.dim() == 2 && b.dim() == 2;
+    bool contig = x0.is_contiguous() && b.is_contiguous();
+    for (const torch::Tensor& w : imgs) {
+        one_gpu = one_gpu && w.is_cuda() && w.device() == x0.device();
+        bf16 = bf16 && w.scalar_type() == torch::kBFloat16;
+        dims = dims && w.dim() == 3;
+        contig = contig && w.is_contiguous();
+    }
+    TORCH_CHECK(one_gpu, who, ": operands must be on one GPU");
+    TORCH_CHECK(bf16, who, ": x0, the weight images and b must be bf16");
+    TORCH_CHECK(dims, who, shapes);
+    TORCH_CHECK(contig, who, ": operands must be contiguous");
+}
+
+static void cross_check_launch(const torch::Tensor& x0, at::TensorList imgs,
+                               long bm, const char* who) {
+    TORCH_CHECK(bm == 0 || bm == 16 || bm == 32, who,
+                ": bm must be 0, 16 or 32");
+    bool aligned = (reinterpret_cast<uintptr_t>(x0.data_ptr()) & 15) == 0;
+    for (const torch::Tensor& w : imgs)
+        aligned = aligned
+            && (reinterpret_cast<uintptr_t>(w.data_ptr()) & 15) == 0;
+    TORCH_CHECK(aligned, who, ": x0 and the images must be 16-byte aligned");
+}
+
+// x0 [M, dp] bf16 with dp = ceil32(d), w an [L, dp, dp] stack of images,
+// b [L, d].
 static void cross_check(const torch::Tensor& x0, const torch::Tensor& w,
                         const torch::Tensor& b, long bm, const char* who) {
-    TORCH_CHECK(x0.is_cuda() && w.is_cuda() && b.is_cuda()
-                && w.device() == x0.device() && b.device() == x0.device(),
-                who, ": operands must be on one GPU");
-    TORCH_CHECK(x0.scalar_type() == torch::kBFloat16
-                && w.scalar_type() == torch::kBFloat16
-                && b.scalar_type() == torch::kBFloat16, who,
-                ": x0, the weight images and b must be bf16");
-    TORCH_CHECK(x0.dim() == 2 && w.dim() == 3 && b.dim() == 2, who,
-                ": x0 [M, dp], images [L, dp, dp], b [L, d]");
-    TORCH_CHECK(x0.is_contiguous() && w.is_contiguous() && b.is_contiguous(),
-                who, ": operands must be contiguous");
+    cross_check_operands(x0, {w}, b,
+                         ": x0 [M, dp], images [L, dp, dp], b [L, d]", who);
     const long M = x0.size(0), dp = x0.size(1), L = b.size(0), d = b.size(1);
     TORCH_CHECK(emb_cross_fits(M, d, dp, L), who, ": needs dp = ceil32(d) in "
                 "32..512, 1 <= L <= 6 and M*dp*(L+1) < 2^31");
     TORCH_CHECK(w.size(0) == L && w.size(1) == dp && w.size(2) == dp, who,
                 ": weight images must be [L, dp, dp]");
-    TORCH_CHECK(bm == 0 || bm == 16 || bm == 32, who,
-                ": bm must be 0, 16 or 32");
-    TORCH_CHECK((reinterpret_cast<uintptr_t>(x0.data_ptr()) & 15) == 0
-                && (reinterpret_cast<uintptr_t>(w.data_ptr()) & 15) == 0,
-                who, ": x0 and the images must be 16-byte aligned");
+    cross_check_launch(x0, {w}, bm, who);
 }
 
 // a mirror the kernels write: contiguous bf16 [n, M, dp] on x0's device
@@ -2166,6 +2190,74 @@ static const void* cross_vec(const OptTensor& t, const torch::Tensor& x0,
     return t->data_ptr();
 }
 
+// The logit head of a forward: with w_out [d] come b_out [1], out [M] fp32
+// and optionally partial [M] fp32; without it none of them. All null in the
+// x_L form.
+struct CrossHead {
+    const void *wo = nullptr, *bo = nullptr;
+    const float* partial = nullptr;
+    float* out = nullptr;
+};
+
+static CrossHead cross_head(const torch::Tensor& x0, long d,
+                            const OptTensor& w_out, const OptTensor& b_out,
+                            const OptTensor& partial, const OptTensor& out,
+                            const char* who) {
+    CrossHead h;
+    const long M = x0.size(0);
+    if (!w_out.has_value()) {
+        TORCH_CHECK(!partial.has_value() && !out.has_value()
+                    && !b_out.has_value(), who,
+                    ": b_out, partial and out belong to w_out");
+        return h;
+    }
+    h.wo = cross_vec(w_out, x0, d, who);
+    h.bo = cross_vec(b_out, x0, 1, who);
+    TORCH_CHECK(out.has_value() && out->is_cuda()
+                && out->device() == x0.device()
+                && out->scalar_type() == torch::kFloat32
+                && out->is_contiguous() && out->dim() == 1
+                && out->size(0) == M, who,
+                ": out must be contiguous fp32 [M]");
+    h.out = out->data_ptr<float>();
+    if (partial.has_value()) {
+        TORCH_CHECK(partial->is_cuda() && partial->device() == x0.device()
+                    && partial->scalar_type() == torch::kFloat32
+                    && partial->is_contiguous() && partial->numel() == M,
+                    who, ": partial must be contiguous fp32 [M]");
+        h.partial = partial->data_ptr<float>();
+    }
+    return h;
+}
+
+// The gradient coming into a backward: (dout [M] fp32, w_out [d]) in the
+// logit form, else gl [M, dp] bf16.
+struct CrossGrad {
+    const float* dout = nullptr;
+    const void *wo = nullptr, *gl = nullptr;
+};
+
+static CrossGrad cross_grad(const torch::Tensor& x0, long d,
+                            const OptTensor& dout, const OptTensor& w_out,
+                            const OptTensor& gl, const char* who) {
+    CrossGrad g;
+    TORCH_CHECK(dout.has_value() == w_out.has_value()
+                && dout.has_value() != gl.has_value(), who,
+                ": either (dout, w_out) or gl");
+    if (dout.has_value()) {
+        TORCH_CHECK(dout->is_cuda() && dout->device() == x0.device()
+                    && dout->scalar_type() == torch::kFloat32
+                    && dout->is_contiguous() && dout->numel() == x0.size(0),
+                    who, ": dout must be contiguous fp32 [M]");
+        g.dout = dout->data_ptr<float>();
+        g.wo = cross_vec(w_out, x0, d, who);
+    } else {
+        cross_check_mirror(gl->unsqueeze(0), x0, 1, who);
+        g.gl = gl->data_ptr();
+    }
+    return g;
+}
+
 // xs: [L, M, dp] (x_1 .. x_L, with us [L, M, dp]: a backward follows), or
 // [1, M, dp] (x_L alone), or none in the logit form. w_out given: the fp32
 // logit [M] is written to out.
@@ -2181,36 +2273,13 @@ void cross_fwd(torch::Tensor x0, torch::Tensor wimg, torch::Tensor b,
     TORCH_CHECK(!save_all || xs.has_value(), "cross_fwd: us needs xs");
     if (xs.has_value())
         cross_check_mirror(*xs, x0, save_all ? L : 1, "cross_fwd");
-    const void *wo = nullptr, *bo = nullptr;
-    const float* pp = nullptr;
-    float* op = nullptr;
-    if (w_out.has_value()) {
-        wo = cross_vec(w_out, x0, d, "cross_fwd");
-        bo = cross_vec(b_out, x0, 1, "cross_fwd");
-        TORCH_CHECK(out.has_value() && out->is_cuda()
-                    && out->device() == x0.device()
-                    && out->scalar_type() == torch::kFloat32
-                    && out->is_contiguous() && out->dim() == 1
-                    && out->size(0) == M,
-                    "cross_fwd: out must be contiguous fp32 [M]");
-        op = out->data_ptr<float>();
-        if (partial.has_value()) {
-            TORCH_CHECK(partial->is_cuda() && partial->device() == x0.device()
-                        && partial->scalar_type() == torch::kFloat32
-                        && partial->is_contiguous() && partial->numel() == M,
-                        "cross_fwd: partial must be contiguous fp32 [M]");
-            pp = partial->data_ptr<float>();
-        }
-    } else {
-        TORCH_CHECK(!partial.has_value() && !out.has_value()
-                    && !b_out.has_value(),
-                    "cross_fwd: b_out, partial and out belong to w_out");
-    }
+    const CrossHead h = cross_head(x0, d, w_out, b_out, partial, out,
+                                   "cross_fwd");
     const c10::cuda::CUDAGuard guard(x0.device());
     emb_cross_fwd(x0.data_ptr(), wimg.data_ptr(), b.data_ptr(), M, d, dp, L,
                   xs.has_value() ? xs->data_ptr() : nullptr,
-                  save_all ? us->data_ptr() : nullptr, save_all ? 1 : 0, wo,
-                  bo, pp, op, (int)bm, cur_stream());
+                  save_all ? us->data_ptr() : nullptr, save_all ? 1 : 0,
+                  h.wo, h.bo, h.partial, h.out, (int)bm, cur_stream());
 }
 
 // wtimg: images of W_l^T. g_L comes from (dout [M] fp32, w_out [d]) in the
@@ -2223,26 +2292,11 @@ void cross_bwd(torch::Tensor x0, torch::Tensor us, torch::Tensor wtimg,
     cross_check_mirror(us, x0, L, "cross_bwd");
     cross_check_mirror(qs, x0, L, "cross_bwd");
     cross_check_mirror(dx0.unsqueeze(0), x0, 1, "cross_bwd");
-    TORCH_CHECK(dout.has_value() == w_out.has_value()
-                && dout.has_value() != gl.has_value(),
-                "cross_bwd: either (dout, w_out) or gl");
-    const float* dp_ = nullptr;
-    const void *wo = nullptr, *gp = nullptr;
-    if (dout.has_value()) {
-        TORCH_CHECK(dout->is_cuda() && dout->device() == x0.device()
-                    && dout->scalar_type() == torch::kFloat32
-                    && dout->is_contiguous() && dout->numel() == M,
-                    "cross_bwd: dout must be contiguous fp32 [M]");
-        dp_ = dout->data_ptr<float>();
-        wo = cross_vec(w_out, x0, d, "cross_bwd");
-    } else {
-        cross_check_mirror(gl->unsqueeze(0), x0, 1, "cross_bwd");
-        gp = gl->data_ptr();
-    }
+    const CrossGrad g = cross_grad(x0, d, dout, w_out, gl, "cross_bwd");
     const c10::cuda::CUDAGuard guard(x0.device());
     emb_cross_bwd(x0.data_ptr(), us.data_ptr(), wtimg.data_ptr(), M, d, dp,
-                  L, dp_, wo, gp, qs.data_ptr(), dx0.data_ptr(), (int)bm,
-                  cur_stream());
+                  L, g.dout, g.wo, g.gl, qs.data_ptr(), dx0.data_ptr(),
+                  (int)bm, cur_stream());
 }
 
 long cross_bm(long M, long bm) { return emb_cross_bm(M, (int)bm); }
@@ -2256,21 +2310,8 @@ long cross_bm(long M, long bm) { return emb_cross_bm(M, (int)bm); }
 static void cross_lr_check(const torch::Tensor& x0, const torch::Tensor& down,
                            const torch::Tensor& up, const torch::Tensor& b,
                            long r, long bm, const char* who) {
-    TORCH_CHECK(x0.is_cuda() && down.is_cuda() && up.is_cuda() && b.is_cuda()
-                && down.device() == x0.device() && up.device() == x0.device()
-                && b.device() == x0.device(),
-                who, ": operands must be on one GPU");
-    TORCH_CHECK(x0.scalar_type() == torch::kBFloat16
-                && down.scalar_type() == torch::kBFloat16
-                && up.scalar_type() == torch::kBFloat16
-                && b.scalar_type() == torch::kBFloat16, who,
-                ": x0, the weight images and b must be bf16");
-    TORCH_CHECK(x0.dim() == 2 && down.dim() == 3 && up.dim() == 3
-                && b.dim() == 2, who,
-                ": x0 [M, dp], images [L, rp, dp] and [L, dp, rp], b [L, d]");
-    TORCH_CHECK(x0.is_contiguous() && down.is_contiguous()
-                && up.is_contiguous() && b.is_contiguous(),
-                who, ": operands must be contiguous");
+    cross_check_operands(x0, {down, up}, b, ": x0 [M, dp], images "
+                         "[L, rp, dp] and [L, dp, rp], b [L, d]", who);
     const long M = x0.size(0), dp = x0.size(1), L = b.size(0), d = b.size(1);
     const long rp = down.size(1);
     TORCH_CHECK(emb_cross_lr_fits(M, d, dp, r, rp, L), who, ": needs dp = "
@@ -2279,12 +2320,7 @@ static void cross_lr_check(const torch::Tensor& x0, const torch::Tensor& down,
     TORCH_CHECK(down.size(0) == L && down.size(2) == dp && up.size(0) == L
                 && up.size(1) == dp && up.size(2) == rp, who,
                 ": weight images must be [L, rp, dp] and [L, dp, rp]");
-    TORCH_CHECK(bm == 0 || bm == 16 || bm == 32, who,
-                ": bm must be 0, 16 or 32");
-    TORCH_CHECK((reinterpret_cast<uintptr_t>(x0.data_ptr()) & 15) == 0
-                && (reinterpret_cast<uintptr_t>(down.data_ptr()) & 15) == 0
-                && (reinterpret_cast<uintptr_t>(up.data_ptr()) & 15) == 0,
-                who, ": x0 and the images must be 16-byte aligned");
+    cross_check_launch(x0, {down, up}, bm, who);
 }
 
 // a rank mirror the kernels write in 16-byte pieces: bf16 [L, M, rp]
@@ -2321,38 +2357,15 @@ void cross_lr_fwd(torch::Tensor x0, torch::Tensor vimg, torch::Tensor uimg,
     }
     if (xs.has_value())
         cross_check_mirror(*xs, x0, save_all ? L : 1, "cross_lr_fwd");
-    const void *wo = nullptr, *bo = nullptr;
-    const float* pp = nullptr;
-    float* op = nullptr;
-    if (w_out.has_value()) {
-        wo = cross_vec(w_out, x0, d, "cross_lr_fwd");
-        bo = cross_vec(b_out, x0, 1, "cross_lr_fwd");
-        TORCH_CHECK(out.has_value() && out->is_cuda()
-                    && out->device() == x0.device()
-                    && out->scalar_type() == torch::kFloat32
-                    && out->is_contiguous() && out->dim() == 1
-                    && out->size(0) == M,
-                    "cross_lr_fwd: out must be contiguous fp32 [M]");
-        op = out->data_ptr<float>();
-        if (partial.has_value()) {
-            TORCH_CHECK(partial->is_cuda() && partial->device() == x0.device()
-                        && partial->scalar_type() == torch::kFloat32
-                        && partial->is_contiguous() && partial->numel() == M,
-                        "cross_lr_fwd: partial must be contiguous fp32 [M]");
-            pp = partial->data_ptr<float>();
-        }
-    } else {
-        TORCH_CHECK(!partial.has_value() && !out.has_value()
-                    && !b_out.has_value(),
-                    "cross_lr_fwd: b_out, partial and out belong to w_out");
-    }
+    const CrossHead h = cross_head(x0, d, w_out, b_out, partial, out,
+                                   "cross_lr_fwd");
     const c10::cuda::CUDAGuard guard(x0.device());
     emb_cross_lr_fwd(x0.data_ptr(), vimg.data_ptr(), uimg.data_ptr(),
                      b.data_ptr(), M, d, dp, r, rp, L,
                      xs.has_value() ? xs->data_ptr() : nullptr,
                      save_all ? us->data_ptr() : nullptr,
                      save_all ? ps->data_ptr() : nullptr, save_all ? 1 : 0,
-                     wo, bo, pp, op, (int)bm, cur_stream());
+                     h.wo, h.bo, h.partial, h.out, (int)bm, cur_stream());
 }
 
 // utimg: images of U_l^T [L, rp, dp], vtimg: of V_l^T [L, dp, rp]. g_L comes
@@ -2370,27 +2383,12 @@ void cross_lr_bwd(torch::Tensor x0, torch::Tensor us, torch::Tensor utimg,
     cross_check_mirror(qs, x0, L, "cross_lr_bwd");
     cross_lr_check_rank(ss, x0, L, rp, "cross_lr_bwd");
     cross_check_mirror(dx0.unsqueeze(0), x0, 1, "cross_lr_bwd");
-    TORCH_CHECK(dout.has_value() == w_out.has_value()
-                && dout.has_value() != gl.has_value(),
-                "cross_lr_bwd: either (dout, w_out) or gl");
-    const float* dp_ = nullptr;
-    const void *wo = nullptr, *gp = nullptr;
-    if (dout.has_value()) {
-        TORCH_CHECK(dout->is_cuda() && dout->device() == x0.device()
-                    && dout->scalar_type() == torch::kFloat32
-                    && dout->is_contiguous() && dout->numel() == M,
-                    "cross_lr_bwd: dout must be contiguous fp32 [M]");
-        dp_ = dout->data_ptr<float>();
-        wo = cross_vec(w_out, x0, d, "cross_lr_bwd");
-    } else {
-        cross_check_mirror(gl->unsqueeze(0), x0, 1, "cross_lr_bwd");
-        gp = gl->data_ptr();
-    }
+    const CrossGrad g = cross_grad(x0, d, dout, w_out, gl, "cross_lr_bwd");
     const c10::cuda::CUDAGuard guard(x0.device());
     emb_cross_lr_bwd(x0.data_ptr(), us.data_ptr(), utimg.data_ptr(),
-                     vtimg.data_ptr(), M, d, dp, r, rp, L, dp_, wo, gp,
-                     qs.data_ptr(), ss.data_ptr(), dx0.data_ptr(), (int)bm,
-                     cur_stream());
+                     vtimg.data_ptr(), M, d, dp, r, rp, L, g.dout, g.wo,
+                     g.gl, qs.data_ptr(), ss.data_ptr(), dx0.data_ptr(),
+                     (int)bm, cur_stream());
 }
 
 long cross_lr_bm(long M, long bm) { return emb_cross_lr_bm(M, (int)bm); }

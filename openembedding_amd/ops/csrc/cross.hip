@@ -64,35 +64,11 @@
 // the backward at BM = 32, KSM = 16 keeps 64 VGPRs of g and a and therefore
 // streams its weights single-buffered.
 
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-#include <cstdint>
-
-typedef __hip_bfloat16 xbf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "cross_common.h"
 
 #define CROSS_WAVES 8
 #define CROSS_PAD 8          // elements behind a tile row (16 bytes)
 
-static __device__ __forceinline__ float cross_f32(unsigned bits16) {
-    return __uint_as_float(bits16 << 16);
-}
-static __device__ __forceinline__ unsigned cross_rne(float v) {
-    return __bfloat16_as_ushort((xbf16)v);      // round to nearest even
-}
-static __device__ __forceinline__ void cross_unpack(uint2 p, float (&f)[4]) {
-    f[0] = __uint_as_float(p.x << 16);
-    f[1] = __uint_as_float(p.x & 0xffff0000u);
-    f[2] = __uint_as_float(p.y << 16);
-    f[3] = __uint_as_float(p.y & 0xffff0000u);
-}
-static __device__ __forceinline__ uint2 cross_pack(const unsigned (&h)[4]) {
-    return make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
-}
-static __device__ __forceinline__ bf16x8 cross_frag(const uint16_t* p) {
-    return *reinterpret_cast<const bf16x8*>(__builtin_assume_aligned(p, 16));
-}
 // logical chunk li of the block -> the chunk it streams
 static __device__ __forceinline__ int cross_rot(int li, int rot, int nch) {
     const int c = li + rot;
@@ -140,34 +116,6 @@ static __device__ __forceinline__ f32x4 cross_tile(const bf16x8 (&b)[KSM],
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                 b[s], AREG ? a[s] : cross_frag(pa + 32 * s), acc, 0, 0, 0);
     return acc;
-}
-
-// The block's rows of x0 [M, dp] -> t0 (and t1): every (row < BM, k < dp) is
-// written, rows >= M and the pad columns k >= d as zeros. 16-byte pieces.
-template <int BM>
-static __device__ __forceinline__ void cross_stage_x0(
-        const uint16_t* __restrict__ x0, int m0, int M, int d, int dp,
-        int LD, uint16_t* t0, uint16_t* t1) {
-    const int ppr = dp >> 3;                 // pieces per row
-    for (int i = threadIdx.x; i < BM * ppr; i += blockDim.x) {
-        const int row = i / ppr, k = (i - row * ppr) * 8;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        const int nv = d - k;                // valid elements of the piece
-        if (m0 + row < M && nv > 0) {
-            v = *reinterpret_cast<const uint4*>(__builtin_assume_aligned(
-                x0 + (m0 + row) * dp + k, 16));
-            if (nv < 8) {
-                unsigned w[4] = {v.x, v.y, v.z, v.w};
-                #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    w[j] = (2 * j < nv ? w[j] & 0xffffu : 0u)
-                         | (2 * j + 1 < nv ? w[j] & 0xffff0000u : 0u);
-                v = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-        }
-        *reinterpret_cast<uint4*>(t0 + row * LD + k) = v;
-        if (t1) *reinterpret_cast<uint4*>(t1 + row * LD + k) = v;
-    }
 }
 
 // ---- forward ----------------------------------------------------------
@@ -477,46 +425,14 @@ void k_cross_bwd(const uint16_t* __restrict__ x0,
 //   16384   57.9 / 43.0    43.9 / 36.3   146.6 / 126.4   109.4 / 108.3
 static int cross_pick_bm(long M, int bm) {
     if (bm == 16 || bm == 32) return bm;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess
-            || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount,
-                                     dev) != hipSuccess || n <= 0)
-            n = 256;
-        cus = n;
-    }
-    return (M + 15) / 16 <= cus ? 16 : 32;
+    return (M + 15) / 16 <= device_cus() ? 16 : 32;
 }
 
-// BM = 32 at dp > 256 needs more than the 64 KB a kernel gets by default
-template <typename K>
-static void cross_allow_lds(K kernel, size_t bytes) {
-    if (bytes > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)bytes);
+// the three tiles: BM = 32 at dp > 256 needs more than the 64 KB a kernel
+// gets by default (allow_lds)
+static size_t cross_lds(int bm, long dp) {
+    return (size_t)3 * bm * (dp + CROSS_PAD) * 2;
 }
-
-#define CROSS_LAUNCH(kernel, ...)                                           \
-    do {                                                                    \
-        const size_t lds = (size_t)3 * bm * (dp + CROSS_PAD) * 2;           \
-        const int grid = (int)((M + bm - 1) / bm);                          \
-        const int ks = (int)(dp / 32);                                      \
-        if (bm == 16) {                                                     \
-            if (ks <= 4) { CROSS_ONE(kernel, 16, 4, __VA_ARGS__) }          \
-            else if (ks <= 8) { CROSS_ONE(kernel, 16, 8, __VA_ARGS__) }     \
-            else { CROSS_ONE(kernel, 16, 16, __VA_ARGS__) }                 \
-        } else {                                                            \
-            if (ks <= 4) { CROSS_ONE(kernel, 32, 4, __VA_ARGS__) }          \
-            else if (ks <= 8) { CROSS_ONE(kernel, 32, 8, __VA_ARGS__) }     \
-            else { CROSS_ONE(kernel, 32, 16, __VA_ARGS__) }                 \
-        }                                                                   \
-    } while (0)
-
-#define CROSS_ONE(kernel, BM_, KSM_, ...)                                   \
-    cross_allow_lds(&kernel<BM_, KSM_>, lds);                               \
-    kernel<BM_, KSM_><<<grid, 64 * CROSS_WAVES, lds, stream>>>(__VA_ARGS__);
 
 extern "C" {
 
@@ -535,6 +451,9 @@ void emb_cross_fwd(const void* x0, const void* wimg, const void* bias,
                    hipStream_t stream) {
     if (M == 0) return;
     bm = cross_pick_bm(M, bm);
+    const size_t lds = cross_lds(bm, dp);
+    const int ks = (int)(dp / 32), grid = (int)((M + bm - 1) / bm);
+    const int block = 64 * CROSS_WAVES;
     CROSS_LAUNCH(k_cross_fwd, (const uint16_t*)x0, (const uint16_t*)wimg,
                  (const uint16_t*)bias, (int)M, (int)d, ks, (int)L,
                  (uint16_t*)xs, (uint16_t*)us, save_all,
@@ -548,6 +467,9 @@ void emb_cross_bwd(const void* x0, const void* us, const void* wtimg, long M,
                    int bm, hipStream_t stream) {
     if (M == 0) return;
     bm = cross_pick_bm(M, bm);
+    const size_t lds = cross_lds(bm, dp);
+    const int ks = (int)(dp / 32), grid = (int)((M + bm - 1) / bm);
+    const int block = 64 * CROSS_WAVES;
     CROSS_LAUNCH(k_cross_bwd, (const uint16_t*)x0, (const uint16_t*)us,
                  (const uint16_t*)wtimg, (int)M, (int)d, ks, (int)L, dout,
                  (const uint16_t*)w_out, (const uint16_t*)gl, (uint16_t*)qs,

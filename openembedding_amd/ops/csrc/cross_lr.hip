@@ -69,65 +69,12 @@
 // of a tile and every (w, row, j < rp) of the partials is written before
 // it is read: no zeroing pass, no uninitialised LDS.
 
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-#include <cstdint>
-
-typedef __hip_bfloat16 xbf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "cross_common.h"
 
 #define CLR_WAVES 8
 #define CLR_PAD 8            // bf16 elements behind a tile row (16 bytes)
 #define CLR_PPAD 4           // floats behind a row of the partials
 #define CLR_RSM 4            // k-steps of the up GEMM at most (rp <= 128)
-
-static __device__ __forceinline__ float clr_f32(unsigned bits16) {
-    return __uint_as_float(bits16 << 16);
-}
-static __device__ __forceinline__ unsigned clr_rne(float v) {
-    return __bfloat16_as_ushort((xbf16)v);      // round to nearest even
-}
-static __device__ __forceinline__ void clr_unpack(uint2 p, float (&f)[4]) {
-    f[0] = __uint_as_float(p.x << 16);
-    f[1] = __uint_as_float(p.x & 0xffff0000u);
-    f[2] = __uint_as_float(p.y << 16);
-    f[3] = __uint_as_float(p.y & 0xffff0000u);
-}
-static __device__ __forceinline__ uint2 clr_pack(const unsigned (&h)[4]) {
-    return make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
-}
-static __device__ __forceinline__ bf16x8 clr_frag(const uint16_t* p) {
-    return *reinterpret_cast<const bf16x8*>(__builtin_assume_aligned(p, 16));
-}
-
-// The block's rows of x0 [M, dp] -> t0 (and t1): every (row < BM, k < dp) is
-// written, rows >= M and the pad columns k >= d as zeros. 16-byte pieces.
-template <int BM>
-static __device__ __forceinline__ void clr_stage_x0(
-        const uint16_t* __restrict__ x0, int m0, int M, int d, int dp,
-        int LD, uint16_t* t0, uint16_t* t1) {
-    const int ppr = dp >> 3;                 // pieces per row
-    for (int i = threadIdx.x; i < BM * ppr; i += blockDim.x) {
-        const int row = i / ppr, k = (i - row * ppr) * 8;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        const int nv = d - k;                // valid elements of the piece
-        if (m0 + row < M && nv > 0) {
-            v = *reinterpret_cast<const uint4*>(__builtin_assume_aligned(
-                x0 + (m0 + row) * dp + k, 16));
-            if (nv < 8) {
-                unsigned w[4] = {v.x, v.y, v.z, v.w};
-                #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    w[j] = (2 * j < nv ? w[j] & 0xffffu : 0u)
-                         | (2 * j + 1 < nv ? w[j] & 0xffff0000u : 0u);
-                v = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-        }
-        *reinterpret_cast<uint4*>(t0 + row * LD + k) = v;
-        if (t1) *reinterpret_cast<uint4*>(t1 + row * LD + k) = v;
-    }
-}
 
 // Down GEMM: part[w][row][j] = sum over the k-steps of part w of
 // img[j][k] * tile[row][k], img one [rp, dp] image, nc = rp / 16 chunks.
@@ -150,16 +97,16 @@ static __device__ __forceinline__ void clr_down(
         // two k-steps a trip, both weight loads in flight before the MFMAs
         for (int s = s0; s < s1; s += 2) {
             const bool two = s + 1 < s1;
-            const bf16x8 b0 = clr_frag(pb + s * 512);
-            const bf16x8 b1 = clr_frag(pb + (two ? s + 1 : s) * 512);
+            const bf16x8 b0 = cross_frag(pb + s * 512);
+            const bf16x8 b1 = cross_frag(pb + (two ? s + 1 : s) * 512);
             #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 const uint16_t* par = pa + rt * 16 * LD + s * 32;
                 acc[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    b0, clr_frag(par), acc[rt], 0, 0, 0);
+                    b0, cross_frag(par), acc[rt], 0, 0, 0);
                 if (two)
                     acc[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        b1, clr_frag(par + 32), acc[rt], 0, 0, 0);
+                        b1, cross_frag(par + 32), acc[rt], 0, 0, 0);
             }
         }
         #pragma unroll
@@ -201,8 +148,8 @@ static __device__ __forceinline__ void clr_rank_frags(
                 unsigned h[8];
                 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    h[i] = j0 + i < r ? clr_rne(lo[i]) : 0u;
-                    h[4 + i] = j0 + 4 + i < r ? clr_rne(hi[i]) : 0u;
+                    h[i] = j0 + i < r ? cross_rne(lo[i]) : 0u;
+                    h[4 + i] = j0 + 4 + i < r ? cross_rne(hi[i]) : 0u;
                 }
                 const uint4 v = make_uint4(h[0] | (h[1] << 16),
                                            h[2] | (h[3] << 16),
@@ -226,7 +173,7 @@ static __device__ __forceinline__ void clr_ld_w(bf16x8 (&b)[CLR_RSM],
                              + (unsigned)(lane * 8);
     #pragma unroll
     for (int s = 0; s < CLR_RSM; ++s)
-        if (s < ksr) b[s] = clr_frag(pb + 512 * s);
+        if (s < ksr) b[s] = cross_frag(pb + 512 * s);
 }
 
 static __device__ __forceinline__ f32x4 clr_up(const bf16x8 (&b)[CLR_RSM],
@@ -273,7 +220,7 @@ void k_cross_lr_fwd(const uint16_t* __restrict__ x0,
     const int rl = lane & 15, g4 = lane >> 4;
     const int MD = M * dp;           // one layer of a [.., M, dp] mirror
 
-    clr_stage_x0<BM>(x0, m0, M, d, dp, LD, tx0, cur);
+    cross_stage_x0<BM>(x0, m0, M, d, dp, LD, tx0, cur);
 
     for (int l = 0; l < L; ++l) {
         const uint16_t* Ul = uimg + l * dp * rp;
@@ -306,21 +253,21 @@ void k_cross_lr_fwd(const uint16_t* __restrict__ x0,
                     const int row = rt * 16 + rl;
                     const int at = row * LD + o0;
                     float x0v[4], xlv[4];
-                    clr_unpack(*reinterpret_cast<const uint2*>(tx0 + at),
-                               x0v);
-                    clr_unpack(*reinterpret_cast<const uint2*>(cur + at),
-                               xlv);
+                    cross_unpack(*reinterpret_cast<const uint2*>(tx0 + at),
+                                 x0v);
+                    cross_unpack(*reinterpret_cast<const uint2*>(cur + at),
+                                 xlv);
                     unsigned uh[4], xh[4];
                     #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const float t = acc[i] + clr_f32(bv[i]);
+                        const float t = acc[i] + cross_f32(bv[i]);
                         float y = x0v[i] * t;
                         y = y + xlv[i];
                         const bool live = o0 + i < d;
-                        uh[i] = live ? clr_rne(t) : 0u;
-                        xh[i] = live ? clr_rne(y) : 0u;
+                        uh[i] = live ? cross_rne(t) : 0u;
+                        xh[i] = live ? cross_rne(y) : 0u;
                     }
-                    const uint2 xp = clr_pack(xh);
+                    const uint2 xp = cross_pack(xh);
                     *reinterpret_cast<uint2*>(nxt + at) = xp;
                     const int gm = m0 + row;
                     if (gm < M) {
@@ -328,7 +275,7 @@ void k_cross_lr_fwd(const uint16_t* __restrict__ x0,
                         if (keep) *reinterpret_cast<uint2*>(xm + go) = xp;
                         if (us)
                             *reinterpret_cast<uint2*>(us + l * MD + go)
-                                = clr_pack(uh);
+                                = cross_pack(uh);
                     }
                 }
             }
@@ -345,12 +292,12 @@ void k_cross_lr_fwd(const uint16_t* __restrict__ x0,
         for (int row = wave; row < BM && m0 + row < M; row += CLR_WAVES) {
             float s = 0.f;
             for (int k = lane; k < d; k += 64)
-                s += clr_f32(w_out[k]) * clr_f32(cur[row * LD + k]);
+                s += cross_f32(w_out[k]) * cross_f32(cur[row * LD + k]);
             #pragma unroll
             for (int off = 32; off; off >>= 1)
                 s += __shfl_down(s, off, 64);
             if (lane == 0) {
-                float v = s + clr_f32(b_out[0]);
+                float v = s + cross_f32(b_out[0]);
                 if (partial) v = v + partial[m0 + row];
                 out[m0 + row] = v;
             }
@@ -389,7 +336,7 @@ void k_cross_lr_bwd(const uint16_t* __restrict__ x0,
     const int rl = lane & 15, g4 = lane >> 4;
     const int MD = M * dp;
 
-    clr_stage_x0<BM>(x0, m0, M, d, dp, LD, tx0, nullptr);
+    cross_stage_x0<BM>(x0, m0, M, d, dp, LD, tx0, nullptr);
     __syncthreads();
 
     // g_L, a = 0 and q_{L-1} for the elements this lane owns
@@ -403,7 +350,7 @@ void k_cross_lr_bwd(const uint16_t* __restrict__ x0,
             if (w_out) {
                 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    if (k0 + i < d) wv[i] = clr_f32(w_out[k0 + i]);
+                    if (k0 + i < d) wv[i] = cross_f32(w_out[k0 + i]);
             }
             #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
@@ -415,22 +362,22 @@ void k_cross_lr_bwd(const uint16_t* __restrict__ x0,
                         const float dv = dout[gm];
                         #pragma unroll
                         for (int i = 0; i < 4; ++i)
-                            gv[i] = clr_f32(clr_rne(dv * wv[i]));
+                            gv[i] = cross_f32(cross_rne(dv * wv[i]));
                     } else {
-                        clr_unpack(*reinterpret_cast<const uint2*>(
+                        cross_unpack(*reinterpret_cast<const uint2*>(
                             gl + gm * dp + k0), gv);
                     }
                 }
-                clr_unpack(*reinterpret_cast<const uint2*>(tx0 + at), x0v);
+                cross_unpack(*reinterpret_cast<const uint2*>(tx0 + at), x0v);
                 unsigned qh[4];
                 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     if (k0 + i >= d) gv[i] = 0.f;
                     a[it][rt][i] = 0.f;
                     g[it][rt][i] = gv[i];
-                    qh[i] = k0 + i < d ? clr_rne(gv[i] * x0v[i]) : 0u;
+                    qh[i] = k0 + i < d ? cross_rne(gv[i] * x0v[i]) : 0u;
                 }
-                const uint2 qp = clr_pack(qh);
+                const uint2 qp = cross_pack(qh);
                 *reinterpret_cast<uint2*>(cur + at) = qp;
                 if (gm < M)
                     *reinterpret_cast<uint2*>(qs + (L - 1) * MD + gm * dp
@@ -472,9 +419,9 @@ void k_cross_lr_bwd(const uint16_t* __restrict__ x0,
                     const int row = rt * 16 + rl, gm = m0 + row;
                     const int at = row * LD + k0;
                     float uv[4], x0v[4];
-                    clr_unpack(up[rt], uv);
-                    clr_unpack(*reinterpret_cast<const uint2*>(tx0 + at),
-                               x0v);
+                    cross_unpack(up[rt], uv);
+                    cross_unpack(*reinterpret_cast<const uint2*>(tx0 + at),
+                                 x0v);
                     unsigned qh[4];
                     #pragma unroll
                     for (int i = 0; i < 4; ++i) {
@@ -482,12 +429,12 @@ void k_cross_lr_bwd(const uint16_t* __restrict__ x0,
                         const float p = gv * uv[i];
                         a[it][rt][i] = a[it][rt][i] + p;
                         const float gn = k0 + i < d
-                            ? clr_f32(clr_rne(acc[i] + gv)) : 0.f;
+                            ? cross_f32(cross_rne(acc[i] + gv)) : 0.f;
                         g[it][rt][i] = gn;
-                        qh[i] = k0 + i < d ? clr_rne(gn * x0v[i]) : 0u;
+                        qh[i] = k0 + i < d ? cross_rne(gn * x0v[i]) : 0u;
                     }
                     if (l > 0) {
-                        const uint2 qp = clr_pack(qh);
+                        const uint2 qp = cross_pack(qh);
                         *reinterpret_cast<uint2*>(nxt + at) = qp;
                         if (gm < M)
                             *reinterpret_cast<uint2*>(qs + (l - 1) * MD
@@ -513,10 +460,10 @@ void k_cross_lr_bwd(const uint16_t* __restrict__ x0,
                 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     h[i] = k0 + i < d
-                        ? clr_rne(a[it][rt][i] + g[it][rt][i]) : 0u;
+                        ? cross_rne(a[it][rt][i] + g[it][rt][i]) : 0u;
                 if (gm < M)
                     *reinterpret_cast<uint2*>(dx0 + gm * dp + k0)
-                        = clr_pack(h);
+                        = cross_pack(h);
             }
         }
     }
@@ -535,16 +482,7 @@ void k_cross_lr_bwd(const uint16_t* __restrict__ x0,
 // M > 8192 has not been measured: 32 there is cross.hip's experience.
 static int clr_pick_bm(long M, int bm) {
     if (bm == 16 || bm == 32) return bm;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess
-            || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount,
-                                     dev) != hipSuccess || n <= 0)
-            n = 256;
-        cus = n;
-    }
-    return (M + 15) / 16 <= 2L * cus ? 16 : 32;
+    return (M + 15) / 16 <= 2L * device_cus() ? 16 : 32;
 }
 
 // k-split of the down GEMM: tasks = rp / 16 chunks x W parts over 8 waves
@@ -553,36 +491,12 @@ static int clr_split(long rp) {
     return CLR_WAVES % nc == 0 ? CLR_WAVES / nc : 4;
 }
 
-// tiles + partials pass the 64 KB a kernel gets by default at dp > 256
-template <typename K>
-static void clr_allow_lds(K kernel, size_t bytes) {
-    if (bytes > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)bytes);
+// tiles + partials: past the 64 KB a kernel gets by default at dp > 256
+// (allow_lds)
+static size_t clr_lds(int bm, long dp, long rp, int nsplit) {
+    return (size_t)3 * bm * (dp + CLR_PAD) * 2
+        + (size_t)nsplit * bm * (rp + CLR_PPAD) * 4;
 }
-
-#define CLR_ONE(kernel, BM_, KSM_, ...)                                     \
-    clr_allow_lds(&kernel<BM_, KSM_>, lds);                                 \
-    kernel<BM_, KSM_><<<grid, 64 * CLR_WAVES, lds, stream>>>(__VA_ARGS__);
-
-#define CLR_LAUNCH(kernel, ...)                                             \
-    do {                                                                    \
-        const int ks = (int)(dp / 32), ksr = (int)(rp / 32);                \
-        const int nsplit = clr_split(rp);                                   \
-        const size_t lds = (size_t)3 * bm * (dp + CLR_PAD) * 2              \
-            + (size_t)nsplit * bm * (rp + CLR_PPAD) * 4;                    \
-        const int grid = (int)((M + bm - 1) / bm);                          \
-        if (bm == 16) {                                                     \
-            if (ks <= 4) { CLR_ONE(kernel, 16, 4, __VA_ARGS__) }            \
-            else if (ks <= 8) { CLR_ONE(kernel, 16, 8, __VA_ARGS__) }       \
-            else { CLR_ONE(kernel, 16, 16, __VA_ARGS__) }                   \
-        } else {                                                            \
-            if (ks <= 4) { CLR_ONE(kernel, 32, 4, __VA_ARGS__) }            \
-            else if (ks <= 8) { CLR_ONE(kernel, 32, 8, __VA_ARGS__) }       \
-            else { CLR_ONE(kernel, 32, 16, __VA_ARGS__) }                   \
-        }                                                                   \
-    } while (0)
 
 extern "C" {
 
@@ -605,7 +519,11 @@ void emb_cross_lr_fwd(const void* x0, const void* vimg, const void* uimg,
                       hipStream_t stream) {
     if (M == 0) return;
     bm = clr_pick_bm(M, bm);
-    CLR_LAUNCH(k_cross_lr_fwd, (const uint16_t*)x0, (const uint16_t*)vimg,
+    const int ks = (int)(dp / 32), ksr = (int)(rp / 32);
+    const int nsplit = clr_split(rp), grid = (int)((M + bm - 1) / bm);
+    const int block = 64 * CLR_WAVES;
+    const size_t lds = clr_lds(bm, dp, rp, nsplit);
+    CROSS_LAUNCH(k_cross_lr_fwd, (const uint16_t*)x0, (const uint16_t*)vimg,
                (const uint16_t*)uimg, (const uint16_t*)bias, (int)M, (int)d,
                ks, (int)r, ksr, nsplit, (int)L, (uint16_t*)xs, (uint16_t*)us,
                (uint16_t*)ps, save_all, (const uint16_t*)w_out,
@@ -619,7 +537,11 @@ void emb_cross_lr_bwd(const void* x0, const void* us, const void* utimg,
                       hipStream_t stream) {
     if (M == 0) return;
     bm = clr_pick_bm(M, bm);
-    CLR_LAUNCH(k_cross_lr_bwd, (const uint16_t*)x0, (const uint16_t*)us,
+    const int ks = (int)(dp / 32), ksr = (int)(rp / 32);
+    const int nsplit = clr_split(rp), grid = (int)((M + bm - 1) / bm);
+    const int block = 64 * CLR_WAVES;
+    const size_t lds = clr_lds(bm, dp, rp, nsplit);
+    CROSS_LAUNCH(k_cross_lr_bwd, (const uint16_t*)x0, (const uint16_t*)us,
                (const uint16_t*)utimg, (const uint16_t*)vtimg, (int)M, (int)d,
                ks, (int)r, ksr, nsplit, (int)L, dout, (const uint16_t*)w_out,
                (const uint16_t*)gl, (uint16_t*)qs, (uint16_t*)ss,

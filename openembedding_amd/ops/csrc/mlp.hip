@@ -26,6 +26,7 @@
 
 #include "dense_tail.h"
 #include "flat_opt.h"
+#include "launch_common.h"
 
 typedef __hip_bfloat16 mbf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -610,15 +611,7 @@ extern "C" void emb_mlp3_bias_bwd(const float* dout, const void* dz1,
 static int mlp_pick_bm(long M, long K0p, int bm, bool bwd, bool frag) {
     if (K0p > MLP_LD - 8) return 16;
     if (bm == 16 || bm == 32 || bm == 64) return bm;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess
-            || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount,
-                                     dev) != hipSuccess || n <= 0)
-            n = 256;
-        cus = n;
-    }
+    const int cus = device_cus();
     static const float t_fwd[3] = {25.3f, 28.2f, 40.8f};
     static const float t_bwd[3] = {32.2f, 39.1f, 61.8f};
     static const float t_fwd_frag[3] = {16.1f, 20.2f, 35.2f};
@@ -636,15 +629,8 @@ static int mlp_pick_bm(long M, long K0p, int bm, bool bwd, bool frag) {
     return best;
 }
 
-// BM = 64 needs 108 KB of LDS, above the 64 KB a kernel gets by default
-template <typename K>
-static void mlp_allow_lds(K kernel, size_t bytes) {
-    if (bytes > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)bytes);
-}
-
+// BM = 64 needs 108 KB of LDS, above the 64 KB a kernel gets by default:
+// allow_lds before each launch
 template <int BM, bool FRAG>
 static void mlp_launch_fwd(const void* x0, long M, long K0p,
                            const void* w1, const void* b1,
@@ -655,7 +641,7 @@ static void mlp_launch_fwd(const void* x0, long M, long K0p,
                            void* a1, void* a2, void* a3, float* out,
                            hipStream_t stream) {
     const size_t lds = 2 * BM * MLP_LD * sizeof(mbf16);
-    mlp_allow_lds(&k_mlp3_fwd<BM, FRAG>, lds);
+    allow_lds(&k_mlp3_fwd<BM, FRAG>, lds);
     const long grid = (M + BM - 1) / BM;
     k_mlp3_fwd<BM, FRAG><<<(int)grid, 64 * MLP_WAVES, lds, stream>>>(
         (const mbf16*)x0, M, K0p, (const mbf16*)w1, (const mbf16*)b1,
@@ -694,7 +680,7 @@ static void mlp_launch_bwd(const float* dout, long M, long K0p,
                            void* dz1, void* dz2, void* dz3, void* dx0,
                            float* bias_out, hipStream_t stream) {
     const size_t lds = 2 * BM * MLP_LD * sizeof(mbf16);
-    mlp_allow_lds(&k_mlp3_bwd<BM, FRAG>, lds);
+    allow_lds(&k_mlp3_bwd<BM, FRAG>, lds);
     const long grid = (M + BM - 1) / BM;
     k_mlp3_bwd<BM, FRAG><<<(int)grid, 64 * MLP_WAVES, lds, stream>>>(
         dout, M, K0p, (const mbf16*)a1, (const mbf16*)a2, (const mbf16*)a3,

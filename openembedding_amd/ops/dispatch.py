@@ -657,9 +657,15 @@ def _cross_torch(x0, W, b, w_out, b_out, partial):
     x = x0v
     for l in range(L):
         x = x0v * torch.nn.functional.linear(x, W[l], b[l]) + x
+    return _cross_torch_tail(x, x0, w_out, b_out, partial)
+
+
+def _cross_torch_tail(x, x0, w_out, b_out, partial):
+    """x_L [M, d] of a torch route -> x_L in x0's shape and dtype, or the
+    fp32 logit."""
     if w_out is None:
         x = x.to(x0.dtype)
-        return torch.nn.functional.pad(x, (0, x0.shape[1] - d))
+        return torch.nn.functional.pad(x, (0, x0.shape[1] - x.shape[1]))
     out = (x @ w_out.reshape(-1, 1)).squeeze(1).float() + b_out.float()
     return out if partial is None else out + partial
 
@@ -691,95 +697,136 @@ def _cross_images(W: torch.Tensor, dp: int, with_t: bool, ext):
     return bufs
 
 
+def _cross_fn_forward(fn, ctx, x0, weights, r, b, w_out, b_out, partial,
+                      save, bm):
+    """The forward of _CrossNetFn and _CrossLRFn (``fn``): the mirrors xs,
+    us and, at rank r > 0, ps; the head's arguments; what the backward
+    needs, on ctx. ``fn.launch_fwd`` packs the weight images and launches."""
+    ext = require_hip()
+    M, dp = x0.shape
+    L = b.shape[0]
+    logit = w_out is not None
+    save = bool(save) and any(ctx.needs_input_grad)
+    weights = tuple(w.contiguous() for w in weights)
+    b = b.contiguous()
+    new = lambda *s, dt=torch.bfloat16: torch.empty(  # noqa: E731
+        *s, dtype=dt, device=x0.device)
+    us = new(L, M, dp) if save else None
+    ps = new(L, M, (r + 31) // 32 * 32) if save and r else None
+    xs = new(L, M, dp) if save else None if logit else new(1, M, dp)
+    out = new(M, dt=torch.float32) if logit else None
+    wo = w_out.reshape(-1).contiguous() if logit else None
+    bufs = fn.launch_fwd(
+        ext, x0, weights, b, save, xs, us, ps, wo,
+        b_out.reshape(-1).contiguous() if logit else None,
+        partial.contiguous() if partial is not None else None, out, bm)
+    if save:
+        ctx.save_for_backward(x0, xs, us, ps, b, wo)
+        ctx.bufs = bufs
+        ctx.bm = bm
+        ctx._params = (*weights, b, w_out, b_out)
+        ctx._has_partial = partial is not None
+    return out if logit else xs[-1]
+
+
+def _cross_fn_backward(fn, ctx, g):
+    """The backward of _CrossNetFn and _CrossLRFn (``fn``). The kernel
+    (``fn.launch_bwd``) gives dx0, q_l and, at low rank, s_l; the weight
+    gradients are ``fn.wgrads``, db_l = sum_m q_l and the head's gradients
+    are library ops here. When every parameter's .grad is bound (the flat
+    optimizer's views) they accumulate in place and autograd gets None, as
+    in _FusedMLP3Fn."""
+    ext = require_hip()
+    x0, xs, us, ps, b, wo = ctx.saved_tensors
+    *weights, _, w_out, b_out = ctx._params
+    nw = len(weights)
+    L, d = b.shape
+    logit = wo is not None
+    qs = torch.empty_like(us)
+    ss = None if ps is None else torch.empty_like(ps)
+    dx0 = torch.empty_like(x0)
+    dout = g.contiguous().float() if logit else None
+    gl = None if logit else g.to(torch.bfloat16).contiguous()
+    fn.launch_bwd(ext, ctx, weights, x0, us, b, dout, wo, gl, qs, ss, dx0)
+    xl = [x0[:, :d]] + [xs[l][:, :d] for l in range(L - 1)]
+    q = qs[:, :, :d]
+    params = [p for p in ctx._params if p is not None]
+    prebound = all(p.is_leaf and p.requires_grad and p.grad is not None
+                   and p.grad.dtype == torch.bfloat16
+                   and p.grad.is_contiguous() for p in params)
+    dpart = dout if ctx._has_partial else None
+    dvec = dout.to(torch.bfloat16).unsqueeze(0) if logit else None
+    if prebound:
+        fn.wgrads(weights, None, q, xl, ss, ps)
+        b.grad.add_(q.sum(1))
+        if logit:
+            w_out.grad.view(1, d).addmm_(dvec, xs[L - 1][:, :d])
+            b_out.grad.add_(dout.sum().to(b_out.grad.dtype))
+        return (dx0,) + (None,) * (nw + 3) + (dpart, None, None)
+    need = ctx.needs_input_grad
+    dws = fn.wgrads(weights, need, q, xl, ss, ps)
+    db = dwo = dbo = None
+    if need[nw + 1]:
+        db = q.sum(1)
+    if logit and need[nw + 2]:
+        dwo = (dvec @ xs[L - 1][:, :d]).view_as(w_out)
+    if logit and need[nw + 3]:
+        dbo = dout.sum().to(b_out.dtype).view_as(b_out)
+    return (dx0, *dws, db, dwo, dbo, dpart, None, None)
+
+
 class _CrossNetFn(torch.autograd.Function):
     """k_cross_fwd / k_cross_bwd. Saved for the backward: x_0, the kernel's
     mirrors x_1 .. x_L and u_0 .. u_{L-1}, and the transposed weight images
     packed by the forward (the weights cannot change before the backward
-    runs). The kernel gives dx0 and q_l; dW_l = q_l^T x_l, db_l = sum_m q_l
-    and the head's gradients are library ops. When every parameter's .grad
-    is bound (the flat optimizer's views) they accumulate in place and
-    autograd gets None, as in _FusedMLP3Fn."""
+    runs). The kernel gives dx0 and q_l; dW_l = q_l^T x_l."""
 
     @staticmethod
     def forward(ctx, x0, W, b, w_out, b_out, partial, save, bm):
-        ext = require_hip()
-        M, dp = x0.shape
-        L = b.shape[0]
-        logit = w_out is not None
-        save = bool(save) and any(ctx.needs_input_grad)
-        W = W.contiguous()
-        b = b.contiguous()
-        bufs = _cross_images(W, dp, save, ext)
-        new = lambda *s, dt=torch.bfloat16: torch.empty(  # noqa: E731
-            *s, dtype=dt, device=x0.device)
-        us = new(L, M, dp) if save else None
-        xs = new(L, M, dp) if save else None if logit else new(1, M, dp)
-        out = new(M, dt=torch.float32) if logit else None
-        wo = w_out.reshape(-1).contiguous() if logit else None
-        ext.cross_fwd(x0, bufs["w"], b, xs, us, wo,
-                      b_out.reshape(-1).contiguous() if logit else None,
-                      partial.contiguous() if partial is not None else None,
-                      out, bm)
-        if save:
-            ctx.save_for_backward(x0, xs, us, b, wo)
-            ctx.bufs = bufs
-            ctx.bm = bm
-            ctx._params = (W, b, w_out, b_out)
-            ctx._has_partial = partial is not None
-        return out if logit else xs[-1]
+        return _cross_fn_forward(_CrossNetFn, ctx, x0, (W,), 0, b, w_out,
+                                 b_out, partial, save, bm)
 
     @staticmethod
     def backward(ctx, g):
-        ext = require_hip()
-        x0, xs, us, b, wo = ctx.saved_tensors
-        W, _, w_out, b_out = ctx._params
-        L, d = b.shape
-        logit = wo is not None
-        qs = torch.empty_like(us)
-        dx0 = torch.empty_like(x0)
-        dout = g.contiguous().float() if logit else None
-        gl = None if logit else g.to(torch.bfloat16).contiguous()
+        return _cross_fn_backward(_CrossNetFn, ctx, g)
+
+    @staticmethod
+    def launch_fwd(ext, x0, weights, b, save, xs, us, ps, wo, bo, partial,
+                   out, bm):
+        bufs = _cross_images(weights[0], x0.shape[1], save, ext)
+        ext.cross_fwd(x0, bufs["w"], b, xs, us, wo, bo, partial, out, bm)
+        return bufs
+
+    @staticmethod
+    def launch_bwd(ext, ctx, weights, x0, us, b, dout, wo, gl, qs, ss, dx0):
         ext.cross_bwd(x0, us, ctx.bufs["wt"], b, dout, wo, gl, qs, dx0,
                       ctx.bm)
-        xl = [x0[:, :d]] + [xs[l][:, :d] for l in range(L - 1)]
-        q = qs[:, :, :d]
-        params = [p for p in ctx._params if p is not None]
-        prebound = all(p.is_leaf and p.requires_grad and p.grad is not None
-                       and p.grad.dtype == torch.bfloat16
-                       and p.grad.is_contiguous() for p in params)
-        dpart = dout if ctx._has_partial else None
-        dvec = dout.to(torch.bfloat16).unsqueeze(0) if logit else None
-        if prebound:
+
+    @staticmethod
+    def wgrads(weights, need, q, xl, ss, ps):
+        """Into W.grad when ``need`` is None, else (dW,)."""
+        (W,), L = weights, q.shape[0]
+        if need is None:
             for l in range(L):
                 W.grad[l].addmm_(q[l].t(), xl[l])
-            b.grad.add_(q.sum(1))
-            if logit:
-                w_out.grad.view(1, d).addmm_(dvec, xs[L - 1][:, :d])
-                b_out.grad.add_(dout.sum().to(b_out.grad.dtype))
-            return dx0, None, None, None, None, dpart, None, None
-        need = ctx.needs_input_grad
-        dW = db = dwo = dbo = None
-        if need[1]:
-            dW = torch.stack([q[l].t() @ xl[l] for l in range(L)])
-        if need[2]:
-            db = q.sum(1)
-        if logit and need[3]:
-            dwo = (dvec @ xs[L - 1][:, :d]).view_as(w_out)
-        if logit and need[4]:
-            dbo = dout.sum().to(b_out.dtype).view_as(b_out)
-        return dx0, dW, db, dwo, dbo, dpart, None, None
+            return None
+        return (torch.stack([q[l].t() @ xl[l] for l in range(L)])
+                if need[1] else None,)
 
 
-def _cross_fits(x0, W, b, w_out, b_out, partial) -> bool:
-    """The limits the binding checks (it refuses everything else)."""
+def _cross_fits(x0, weights, b, w_out, b_out, partial, rp=0) -> bool:
+    """The limits the bindings check (they refuse everything else), for the
+    full-rank network (rp = 0) and the low-rank one (rp = ceil32(r))."""
     bf = torch.bfloat16
-    if not (_use_hip(x0) and x0.dtype == W.dtype == b.dtype == bf
-            and x0.is_contiguous() and W.device == b.device == x0.device):
+    if not (_use_hip(x0) and x0.is_contiguous()
+            and all(t.dtype == bf and t.device == x0.device
+                    for t in (x0, b, *weights))):
         return False
     M, dp = x0.shape
     L, d = b.shape
-    if not (dp == (d + 31) // 32 * 32 and 32 <= dp <= 512 and 1 <= L <= 6
-            and M * dp * (L + 1) < 2 ** 31 and x0.data_ptr() % 16 == 0):
+    if not (dp == (d + 31) // 32 * 32 and 32 <= dp <= 512 and rp <= 128
+            and 1 <= L <= 6 and M * max(dp, rp) * (L + 1) < 2 ** 31
+            and x0.data_ptr() % 16 == 0):
         return False
     if w_out is None:
         return True
@@ -813,7 +860,7 @@ def cross_network(x0: torch.Tensor, W: torch.Tensor, b: torch.Tensor,
             or (partial is not None and w_out is None)):
         raise ValueError("cross_network takes x0 [M, d or ceil32(d)], "
                          "W [L, d, d], b [L, d], w_out [d] with b_out [1]")
-    if (_CROSS and _cross_fits(x0, W, b, w_out, b_out, partial)
+    if (_CROSS and _cross_fits(x0, (W,), b, w_out, b_out, partial)
             and require_hip() is not None):
         return _CrossNetFn.apply(x0, W, b, w_out, b_out, partial,
                                  torch.is_grad_enabled(), bm)
@@ -837,11 +884,7 @@ def _cross_lr_torch(x0, U, V, b, w_out, b_out, partial):
     lin = torch.nn.functional.linear
     for l in range(L):
         x = x0v * lin(lin(x, V[l]), U[l], b[l]) + x
-    if w_out is None:
-        x = x.to(x0.dtype)
-        return torch.nn.functional.pad(x, (0, x0.shape[1] - d))
-    out = (x @ w_out.reshape(-1, 1)).squeeze(1).float() + b_out.float()
-    return out if partial is None else out + partial
+    return _cross_torch_tail(x, x0, w_out, b_out, partial)
 
 
 def _cross_lr_images(U: torch.Tensor, V: torch.Tensor, dp: int, rp: int,
@@ -874,106 +917,51 @@ class _CrossLRFn(torch.autograd.Function):
     """k_cross_lr_fwd / k_cross_lr_bwd. Saved for the backward: x_0, the
     kernel's mirrors x_1 .. x_L, u_l and p_l, and the transposed weight
     images packed by the forward. The kernel gives dx0, q_l and s_l;
-    dU_l = q_l^T p_l, dV_l = s_l^T x_l, db_l = sum_m q_l and the head's
-    gradients are library ops. When every parameter's .grad is bound they
-    accumulate in place and autograd gets None, as in _CrossNetFn."""
+    dU_l = q_l^T p_l, dV_l = s_l^T x_l. The rest as in _CrossNetFn."""
 
     @staticmethod
     def forward(ctx, x0, U, V, b, w_out, b_out, partial, save, bm):
-        ext = require_hip()
-        M, dp = x0.shape
-        L, r = V.shape[0], V.shape[1]
-        rp = (r + 31) // 32 * 32
-        logit = w_out is not None
-        save = bool(save) and any(ctx.needs_input_grad)
-        U, V, b = U.contiguous(), V.contiguous(), b.contiguous()
-        bufs = _cross_lr_images(U, V, dp, rp, save, ext)
-        new = lambda *s, dt=torch.bfloat16: torch.empty(  # noqa: E731
-            *s, dtype=dt, device=x0.device)
-        us = new(L, M, dp) if save else None
-        ps = new(L, M, rp) if save else None
-        xs = new(L, M, dp) if save else None if logit else new(1, M, dp)
-        out = new(M, dt=torch.float32) if logit else None
-        wo = w_out.reshape(-1).contiguous() if logit else None
-        ext.cross_lr_fwd(x0, bufs["v"], bufs["u"], b, r, xs, us, ps, wo,
-                         b_out.reshape(-1).contiguous() if logit else None,
-                         partial.contiguous() if partial is not None
-                         else None, out, bm)
-        if save:
-            ctx.save_for_backward(x0, xs, us, ps, b, wo)
-            ctx.bufs = bufs
-            ctx.bm = bm
-            ctx._params = (U, V, b, w_out, b_out)
-            ctx._has_partial = partial is not None
-        return out if logit else xs[-1]
+        return _cross_fn_forward(_CrossLRFn, ctx, x0, (U, V), V.shape[1], b,
+                                 w_out, b_out, partial, save, bm)
 
     @staticmethod
     def backward(ctx, g):
-        ext = require_hip()
-        x0, xs, us, ps, b, wo = ctx.saved_tensors
-        U, V, _, w_out, b_out = ctx._params
-        L, d = b.shape
+        return _cross_fn_backward(_CrossLRFn, ctx, g)
+
+    @staticmethod
+    def launch_fwd(ext, x0, weights, b, save, xs, us, ps, wo, bo, partial,
+                   out, bm):
+        U, V = weights
         r = V.shape[1]
-        logit = wo is not None
-        qs = torch.empty_like(us)
-        ss = torch.empty_like(ps)
-        dx0 = torch.empty_like(x0)
-        dout = g.contiguous().float() if logit else None
-        gl = None if logit else g.to(torch.bfloat16).contiguous()
-        ext.cross_lr_bwd(x0, us, ctx.bufs["ut"], ctx.bufs["vt"], b, r, dout,
-                         wo, gl, qs, ss, dx0, ctx.bm)
-        xl = [x0[:, :d]] + [xs[l][:, :d] for l in range(L - 1)]
-        q, s, p = qs[:, :, :d], ss[:, :, :r], ps[:, :, :r]
-        params = [t for t in ctx._params if t is not None]
-        prebound = all(t.is_leaf and t.requires_grad and t.grad is not None
-                       and t.grad.dtype == torch.bfloat16
-                       and t.grad.is_contiguous() for t in params)
-        dpart = dout if ctx._has_partial else None
-        dvec = dout.to(torch.bfloat16).unsqueeze(0) if logit else None
-        if prebound:
+        bufs = _cross_lr_images(U, V, x0.shape[1], (r + 31) // 32 * 32, save,
+                                ext)
+        ext.cross_lr_fwd(x0, bufs["v"], bufs["u"], b, r, xs, us, ps, wo, bo,
+                         partial, out, bm)
+        return bufs
+
+    @staticmethod
+    def launch_bwd(ext, ctx, weights, x0, us, b, dout, wo, gl, qs, ss, dx0):
+        ext.cross_lr_bwd(x0, us, ctx.bufs["ut"], ctx.bufs["vt"], b,
+                         weights[1].shape[1], dout, wo, gl, qs, ss, dx0,
+                         ctx.bm)
+
+    @staticmethod
+    def wgrads(weights, need, q, xl, ss, ps):
+        """Into U.grad and V.grad when ``need`` is None, else (dU, dV)."""
+        (U, V), L = weights, q.shape[0]
+        r = V.shape[1]
+        s, p = ss[:, :, :r], ps[:, :, :r]
+        if need is None:
             for l in range(L):
                 U.grad[l].addmm_(q[l].t(), p[l])
                 V.grad[l].addmm_(s[l].t(), xl[l])
-            b.grad.add_(q.sum(1))
-            if logit:
-                w_out.grad.view(1, d).addmm_(dvec, xs[L - 1][:, :d])
-                b_out.grad.add_(dout.sum().to(b_out.grad.dtype))
-            return dx0, None, None, None, None, None, dpart, None, None
-        need = ctx.needs_input_grad
-        dU = dV = db = dwo = dbo = None
+            return None
+        dU = dV = None
         if need[1]:
             dU = torch.stack([q[l].t() @ p[l] for l in range(L)])
         if need[2]:
             dV = torch.stack([s[l].t() @ xl[l] for l in range(L)])
-        if need[3]:
-            db = q.sum(1)
-        if logit and need[4]:
-            dwo = (dvec @ xs[L - 1][:, :d]).view_as(w_out)
-        if logit and need[5]:
-            dbo = dout.sum().to(b_out.dtype).view_as(b_out)
-        return dx0, dU, dV, db, dwo, dbo, dpart, None, None
-
-
-def _cross_lr_fits(x0, U, V, b, w_out, b_out, partial) -> bool:
-    """The limits the binding checks (it refuses everything else)."""
-    bf = torch.bfloat16
-    if not (_use_hip(x0) and x0.dtype == U.dtype == V.dtype == b.dtype == bf
-            and x0.is_contiguous()
-            and U.device == V.device == b.device == x0.device):
-        return False
-    M, dp = x0.shape
-    L, d = b.shape
-    rp = (V.shape[1] + 31) // 32 * 32
-    if not (dp == (d + 31) // 32 * 32 and 32 <= dp <= 512 and rp <= 128
-            and 1 <= L <= 6 and M * max(dp, rp) * (L + 1) < 2 ** 31
-            and x0.data_ptr() % 16 == 0):
-        return False
-    if w_out is None:
-        return True
-    return (w_out.dtype == b_out.dtype == bf
-            and w_out.device == b_out.device == x0.device
-            and (partial is None or (partial.dtype == torch.float32
-                                     and partial.device == x0.device)))
+        return dU, dV
 
 
 def cross_network_lr(x0: torch.Tensor, U: torch.Tensor, V: torch.Tensor,
@@ -1010,7 +998,8 @@ def cross_network_lr(x0: torch.Tensor, U: torch.Tensor, V: torch.Tensor,
         raise ValueError("cross_network_lr takes x0 [M, d or ceil32(d)], "
                          "U [L, d, r], V [L, r, d], b [L, d], w_out [d] "
                          "with b_out [1]")
-    if (_CROSS_LR and _cross_lr_fits(x0, U, V, b, w_out, b_out, partial)
+    if (_CROSS_LR and _cross_fits(x0, (U, V), b, w_out, b_out, partial,
+                                  (V.shape[1] + 31) // 32 * 32)
             and require_hip() is not None):
         return _CrossLRFn.apply(x0, U, V, b, w_out, b_out, partial,
                                 torch.is_grad_enabled(), bm)
