@@ -20,7 +20,8 @@ import torch
 import torch.nn as nn
 
 from ..ops import hip_available
-from ..ops.dispatch import cross_network, cross_network_lr, dot_interact
+from ..ops.dispatch import (cross_network, cross_network_lr, dot_interact,
+                            mlp_tower)
 from ..torch import CombinedEmbedding
 from .criteo import CRITEO_FIELD_VOCABS, N_DENSE
 
@@ -310,6 +311,10 @@ class _DNNHead(nn.Module):
         # whole-MLP fused kernel (mlp.hip): enabled by convert_mlp_bf16 when
         # the dnn matches Linear/ReLU x3 + Linear(H,1), H <= 416 (% 16)
         self.fused_mlp = False
+        # fused tower (tower.hip): enabled by convert_mlp_bf16 for every
+        # other Linear/ReLU x (1..4) + Linear(H_L,1) with widths % 16 == 0
+        # in 16..512 over a padded row <= 512 wide
+        self.fused_tower = False
         # fused cross network (cross.hip): enabled by convert_mlp_bf16 for
         # a DCN whose padded row is <= 512 wide with <= 6 cross layers
         self.fused_cross = False
@@ -346,6 +351,12 @@ class _DNNHead(nn.Module):
             return _FusedMLP3Fn.apply(
                 deep_in, partial, l1.weight, l1.bias, l2.weight, l2.bias,
                 l3.weight, l3.bias, l4.weight, l4.bias, self._w1pad)
+        if (self.fused_tower and deep_in.is_cuda
+                and deep_in.dtype == torch.bfloat16):
+            hidden, head = self.dnn[0:-1:2], self.dnn[-1]
+            return mlp_tower(deep_in, [m.weight for m in hidden],
+                             [m.bias for m in hidden], head.weight, head.bias,
+                             partial)
         w_dtype = next(self.dnn.parameters()).dtype
         out = self.dnn(deep_in.to(w_dtype)).squeeze(-1).float()
         return out if partial is None else partial + out
@@ -390,7 +401,8 @@ class _CTRBase(_DNNHead):
         e_all = self.embedding(sparse)
         deep_in, partial = _FusedCTRHeadFn.apply(
             e_all, dense, self.dense_linear.weight, self.dense_linear.bias,
-            use_fm, self.head_bf16, self.fused_mlp or self.fused_cross)
+            use_fm, self.head_bf16,
+            self.fused_mlp or self.fused_tower or self.fused_cross)
         return e_all, deep_in, partial
 
 
@@ -655,7 +667,8 @@ class DLRM(_DNNHead):
     def forward(self, dense: torch.Tensor, sparse: torch.Tensor) -> torch.Tensor:
         x = self.bottom_mlp(dense)                       # [B, dim]
         e = self.embedding(sparse)                       # [B, F, dim]
-        fused = self.fused_mlp and self.head_bf16 and x.is_cuda
+        fused = ((self.fused_mlp or self.fused_tower) and self.head_bf16
+                 and x.is_cuda)
         deep_in = dot_interact(e, x, out_bf16=fused, pad32=fused)
         return self._dnn_out(deep_in)
 
@@ -722,8 +735,9 @@ class DCN(_CTRBase):
             e, lin = self._embed(sparse)
             deep_in = torch.cat([e.flatten(1), dense], dim=1)
             partial = self._first_order(dense, lin)
-        # a padded row goes to the fused MLP alone
-        unpad = (lambda t: t) if self.fused_mlp else (lambda t: t[:, :d])
+        # a padded row goes to the fused MLP or tower alone
+        unpad = ((lambda t: t) if self.fused_mlp or self.fused_tower
+                 else (lambda t: t[:, :d]))
         if self.structure == "parallel":
             logit = cross(deep_in, *ws, self.cross_b, self.cross_out.weight,
                           self.cross_out.bias, partial)
@@ -749,6 +763,17 @@ def convert_mlp_bf16(model: _DNNHead) -> _DNNHead:
               and seq[0].out_features % 16 == 0
               and seq[0].out_features <= 416)
         model.fused_mlp = ok
+        # every other tower the fused tower kernels take (ops.mlp_tower)
+        lin, act = seq[0::2], seq[1::2]
+        widths = [m.out_features for m in lin[:-1]
+                  if isinstance(m, nn.Linear)]
+        model.fused_tower = (
+            not ok and len(seq) % 2 == 1 and 1 <= len(lin) - 1 <= 4
+            and all(isinstance(m, nn.Linear) for m in lin)
+            and all(isinstance(m, nn.ReLU) for m in act)
+            and lin[-1].out_features == 1
+            and all(h % 16 == 0 and 16 <= h <= 512 for h in widths)
+            and (lin[0].in_features + 31) // 32 * 32 <= 512)
     model.head_bf16 = True
     if hasattr(model, "cross_b"):
         # the cross parameters live in bf16 like the dnn's; the kernels

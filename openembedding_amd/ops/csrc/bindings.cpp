@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "dense_tail.h"
+#include "tower.h"
 
 // torch instantiates data_ptr<int64_t> (long on LP64); the kernel TU uses
 // long long — same width, C linkage, so the pointer casts below are safe.
@@ -141,6 +142,14 @@ void emb_cross_lr_bwd(const void*, const void*, const void*, const void*,
                       long, long, long, long, long, long, const float*,
                       const void*, const void*, void*, void*, void*, int,
                       hipStream_t_);
+int emb_tower_fits(long, long, long, long, const long*);
+int emb_tower_bm(long, int);
+int emb_tower_split(int, int);
+void emb_tower_fwd(const TowerArgs*, const void*, long, long, long,
+                   const void*, const void*, const float*, float*, int,
+                   hipStream_t_);
+void emb_tower_bwd(const TowerArgs*, const float*, const void*, const void*,
+                   void*, long, long, int, hipStream_t_);
 void emb_mlp3_bias_bwd(const float*, const void*, const void*, const void*,
                        const void*, long, long, float*, void*, void*, void*,
                        void*, void*, int, int, int, hipStream_t_);
@@ -2393,6 +2402,161 @@ void cross_lr_bwd(torch::Tensor x0, torch::Tensor us, torch::Tensor utimg,
 
 long cross_lr_bm(long M, long bm) { return emb_cross_lr_bm(M, (int)bm); }
 
+// ---- fused MLP tower (tower.hip) -----------------------------------------
+
+// Everything the kernels rely on is checked before a launch; the Python side
+// (ops.mlp_tower) tests the same limits and routes the rest to torch.
+
+// a bf16 matrix [rows, cols] on `like`'s device, contiguous and 16-byte
+// aligned: an image, a mirror or dx0
+static void tower_check_mat(const torch::Tensor& t, const torch::Tensor& like,
+                            long rows, long cols, const char* what,
+                            const char* who) {
+    TORCH_CHECK(t.is_cuda() && t.device() == like.device()
+                && t.scalar_type() == torch::kBFloat16 && t.is_contiguous()
+                && t.dim() == 2 && t.size(0) == rows && t.size(1) == cols
+                && (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0,
+                who, ": ", what, " must be contiguous 16-byte-aligned bf16 [",
+                rows, ", ", cols, "] on one GPU");
+}
+
+// a bf16 vector of n elements on `like`'s device
+static void tower_check_vec(const torch::Tensor& t, const torch::Tensor& like,
+                            long n, const char* what, const char* who) {
+    TORCH_CHECK(t.is_cuda() && t.device() == like.device()
+                && t.scalar_type() == torch::kBFloat16 && t.is_contiguous()
+                && t.numel() == n, who, ": ", what,
+                " must be contiguous bf16 with ", n, " elements");
+}
+
+static void tower_check_f32(const torch::Tensor& t, const torch::Tensor& like,
+                            long M, const char* what, const char* who) {
+    TORCH_CHECK(t.is_cuda() && t.device() == like.device()
+                && t.scalar_type() == torch::kFloat32 && t.is_contiguous()
+                && t.numel() == M, who, ": ", what,
+                " must be contiguous fp32 [M]");
+}
+
+// the limits of the shapes: K0p = ceil32(K0) <= 512, 1 <= L <= 4, every
+// width a multiple of 16 in 16..512, 32-bit indices
+static void tower_check_shape(long M, long K0, long K0p,
+                              const std::vector<long>& h, long bm,
+                              const char* who) {
+    const long L = (long)h.size();
+    TORCH_CHECK(L >= 1 && L <= TOWER_MAXL, who, ": needs 1 <= L <= 4 hidden "
+                "layers, got ", L);
+    TORCH_CHECK(K0 >= 1 && K0p == (K0 + 31) / 32 * 32 && K0p <= 512, who,
+                ": needs x0 [M, K0p] with K0p = ceil32(K0) <= 512, got K0 = ",
+                K0, ", K0p = ", K0p);
+    for (long v : h)
+        TORCH_CHECK(v % 16 == 0 && v >= 16 && v <= 512, who, ": every width "
+                    "must be a multiple of 16 in 16..512, got ", v);
+    TORCH_CHECK(emb_tower_fits(M, K0, K0p, L, h.data()), who,
+                ": needs M*512*(L+1) < 2^31");
+    TORCH_CHECK(bm == 0 || bm == 16 || bm == 32, who,
+                ": bm must be 0, 16 or 32");
+}
+
+static long ceil32(long v) { return (v + 31) / 32 * 32; }
+
+// wimgs[l]: the image of W_{l+1} padded to [H_{l+1}, ceil32(H_l)]
+// (mlp3_pack_frag), H_0 = K0; biases[l] [H_{l+1}]; acts: the mirrors
+// [M, H_{l+1}] to write, or none when no backward follows. Writes the fp32
+// logit [M] to out.
+void tower_fwd(torch::Tensor x0, long K0, std::vector<torch::Tensor> wimgs,
+               std::vector<torch::Tensor> biases,
+               std::vector<torch::Tensor> acts, torch::Tensor w_out,
+               torch::Tensor b_out, OptTensor partial, torch::Tensor out,
+               long bm) {
+    const char* who = "tower_fwd";
+    TORCH_CHECK(x0.is_cuda() && x0.scalar_type() == torch::kBFloat16, who,
+                ": x0 must be bf16 on a GPU");
+    TORCH_CHECK(x0.dim() == 2 && x0.is_contiguous()
+                && (reinterpret_cast<uintptr_t>(x0.data_ptr()) & 15) == 0,
+                who, ": x0 must be contiguous [M, K0p], 16-byte aligned");
+    const long M = x0.size(0), K0p = x0.size(1), L = (long)wimgs.size();
+    TORCH_CHECK(biases.size() == wimgs.size()
+                && (acts.empty() || acts.size() == wimgs.size()), who,
+                ": one bias and (when given) one mirror per image");
+    std::vector<long> h;
+    for (const torch::Tensor& w : wimgs) {
+        TORCH_CHECK(w.dim() == 2, who, ": an image is [H_l, ceil32(H_l-1)]");
+        h.push_back(w.size(0));
+    }
+    tower_check_shape(M, K0, K0p, h, bm, who);
+    TowerArgs a{};
+    a.L = (int)L;
+    long kp = K0p;
+    for (long l = 0; l < L; ++l) {
+        tower_check_mat(wimgs[l], x0, h[l], kp, "a weight image", who);
+        tower_check_vec(biases[l], x0, h[l], "a bias", who);
+        if (!acts.empty())
+            tower_check_mat(acts[l], x0, M, h[l], "a mirror", who);
+        a.st[l] = {wimgs[l].data_ptr(), biases[l].data_ptr(),
+                   acts.empty() ? nullptr : acts[l].data_ptr(), (int)h[l],
+                   (int)(kp / 32), 1, (int)(kp / 32)};
+        kp = ceil32(h[l]);
+    }
+    tower_check_vec(w_out, x0, h[L - 1], "w_out", who);
+    tower_check_vec(b_out, x0, 1, "b_out", who);
+    tower_check_f32(out, x0, M, "out", who);
+    if (partial.has_value()) tower_check_f32(*partial, x0, M, "partial", who);
+    const c10::cuda::CUDAGuard guard(x0.device());
+    emb_tower_fwd(&a, x0.data_ptr(), M, K0, K0p, w_out.data_ptr(),
+                  b_out.data_ptr(),
+                  partial.has_value() ? partial->data_ptr<float>() : nullptr,
+                  out.data_ptr<float>(), (int)bm, cur_stream());
+}
+
+// acts[l]: the forward's mirrors [M, H_{l+1}]; wtimgs[l]: the image of
+// W_{l+1}^T padded to [H_l, ceil32(H_{l+1})], [K0p, ..] for l = 0. Writes
+// dzs[l] [M, H_{l+1}] and dx0 [M, K0p].
+void tower_bwd(long K0, std::vector<torch::Tensor> acts,
+               std::vector<torch::Tensor> wtimgs, torch::Tensor dout,
+               torch::Tensor w_out, std::vector<torch::Tensor> dzs,
+               torch::Tensor dx0, long bm) {
+    const char* who = "tower_bwd";
+    TORCH_CHECK(dx0.is_cuda() && dx0.dim() == 2, who,
+                ": dx0 must be [M, K0p] on a GPU");
+    const long M = dx0.size(0), K0p = dx0.size(1), L = (long)acts.size();
+    TORCH_CHECK(wtimgs.size() == acts.size() && dzs.size() == acts.size(),
+                who, ": one image and one dz per mirror");
+    std::vector<long> h;
+    for (const torch::Tensor& t : acts) {
+        TORCH_CHECK(t.dim() == 2, who, ": a mirror is [M, H_l]");
+        h.push_back(t.size(1));
+    }
+    tower_check_shape(M, K0, K0p, h, bm, who);
+    tower_check_mat(dx0, dx0, M, K0p, "dx0", who);
+    TowerArgs a{};
+    a.L = (int)L;
+    for (long l = L - 1; l >= 0; --l) {
+        const long n = l ? h[l - 1] : K0p, kp = ceil32(h[l]);
+        tower_check_mat(acts[l], dx0, M, h[l], "a mirror", who);
+        tower_check_mat(dzs[l], dx0, M, h[l], "a dz", who);
+        tower_check_mat(wtimgs[l], dx0, n, kp, "a transposed image", who);
+        a.st[L - 1 - l] = {wtimgs[l].data_ptr(),
+                           l ? acts[l - 1].data_ptr() : nullptr,
+                           l ? dzs[l - 1].data_ptr() : dx0.data_ptr(), (int)n,
+                           (int)(kp / 32), 1, (int)(kp / 32)};
+    }
+    tower_check_vec(w_out, dx0, h[L - 1], "w_out", who);
+    tower_check_f32(dout, dx0, M, "dout", who);
+    const c10::cuda::CUDAGuard guard(dx0.device());
+    emb_tower_bwd(&a, dout.data_ptr<float>(), w_out.data_ptr(),
+                  acts[L - 1].data_ptr(), dzs[L - 1].data_ptr(), h[L - 1], M,
+                  (int)bm, cur_stream());
+}
+
+long tower_bm(long M, long bm) { return emb_tower_bm(M, (int)bm); }
+
+// the k-split of a stage with n output columns over a contraction of k
+long tower_split(long n, long k) {
+    TORCH_CHECK(n % 16 == 0 && n >= 16 && n <= 512 && k >= 1 && k <= 512,
+                "tower_split: n a multiple of 16 in 16..512, k in 1..512");
+    return emb_tower_split((int)n, (int)(ceil32(k) / 32));
+}
+
 // ---- CIN implicit-GEMM -------------------------------------------------
 
 torch::Tensor cin_fwd(torch::Tensor x0p, torch::Tensor xkp,
@@ -3165,6 +3329,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("cross_lr_bm", &cross_lr_bm,
           "rows per block the low-rank cross kernels' launcher picks",
           pybind11::arg("M"), pybind11::arg("bm") = 0);
+    m.def("tower_fwd", &tower_fwd,
+          "MLP tower fwd: 1..4 hidden layers of unequal widths and the logit "
+          "head in one launch on MFMA; writes the mirrors it is given",
+          pybind11::arg("x0"), pybind11::arg("K0"), pybind11::arg("wimgs"),
+          pybind11::arg("biases"), pybind11::arg("acts"),
+          pybind11::arg("w_out"), pybind11::arg("b_out"),
+          pybind11::arg("partial"), pybind11::arg("out"),
+          pybind11::arg("bm") = 0);
+    m.def("tower_bwd", &tower_bwd,
+          "MLP tower dgrad chain: dz_1 .. dz_L and dx0 in one launch, no "
+          "atomics",
+          pybind11::arg("K0"), pybind11::arg("acts"), pybind11::arg("wtimgs"),
+          pybind11::arg("dout"), pybind11::arg("w_out"), pybind11::arg("dzs"),
+          pybind11::arg("dx0"), pybind11::arg("bm") = 0);
+    m.def("tower_bm", &tower_bm,
+          "rows per block the tower kernels' launcher picks for M rows",
+          pybind11::arg("M"), pybind11::arg("bm") = 0);
+    m.def("tower_split", &tower_split,
+          "runs the tower kernels cut a stage's contraction into",
+          pybind11::arg("n"), pybind11::arg("k"));
     m.def("cin_fwd", &cin_fwd,
           "CIN layer forward: implicit outer-product MFMA GEMM");
     m.def("cin_dw", &cin_dw,

@@ -1006,6 +1006,183 @@ def cross_network_lr(x0: torch.Tensor, U: torch.Tensor, V: torch.Tensor,
     return _cross_lr_torch(x0, U, V, b, w_out, b_out, partial)
 
 
+# ------------------------------------------------------- fused MLP tower
+# a_l = relu(W_l a_{l-1} + b_l) for l = 1 .. L, then w_out . a_L + b_out
+# (+ partial). ops/csrc/tower.hip runs 1 to 4 hidden layers of unequal widths
+# in one launch each way; OEAMD_TOWER=0 keeps the torch route on the GPU in
+# the same build (A/B runs). Read once at import.
+_TOWER = os.environ.get("OEAMD_TOWER", "1") != "0"
+
+
+def _ceil32(v: int) -> int:
+    return (v + 31) // 32 * 32
+
+
+def _tower_torch(x0, weights, biases, w_out, b_out, partial):
+    """The definition of the operator: plain differentiable ops in the
+    parameters' dtype."""
+    a = x0[:, :weights[0].shape[1]].to(weights[0].dtype)
+    for W, b in zip(weights, biases):
+        a = torch.relu(torch.nn.functional.linear(a, W, b))
+    out = (a @ w_out.reshape(-1, 1)).squeeze(1).float() + b_out.float()
+    return out if partial is None else out + partial
+
+
+def _tower_images(weights, K0p: int, with_t: bool, ext):
+    """The fragment-major images of W_l padded to [H_l, ceil32(H_{l-1})] and
+    (with_t) of W_l^T padded to [H_{l-1}, ceil32(H_l)] ([K0p, ..] for the
+    first layer), cached on the first weight and rewritten every forward by
+    mlp3_pack_frag, six matrices per launch."""
+    W1 = weights[0]
+    key = (K0p, tuple(w.shape for w in weights), W1.device)
+    bufs = getattr(W1, "_tower_bufs", None)
+    if bufs is None or bufs["key"] != key:
+        new = lambda *s: torch.empty(*s, dtype=torch.bfloat16,  # noqa: E731
+                                     device=W1.device)
+        kp = [K0p] + [_ceil32(w.shape[0]) for w in weights[:-1]]
+        rows = [K0p] + [w.shape[0] for w in weights[:-1]]
+        bufs = {"key": key,
+                "w": [new(w.shape[0], k) for w, k in zip(weights, kp)],
+                "wt": [new(r, _ceil32(w.shape[0]))
+                       for w, r in zip(weights, rows)]}
+        W1._tower_bufs = bufs
+    jobs = [(w, d, False) for w, d in zip(weights, bufs["w"])]
+    if with_t:
+        jobs += [(w, d, True) for w, d in zip(weights, bufs["wt"])]
+    for i in range(0, len(jobs), 6):
+        src, dst, tr = zip(*jobs[i:i + 6])
+        ext.mlp3_pack_frag(list(src), list(dst), list(tr))
+    return bufs
+
+
+class _TowerFn(torch.autograd.Function):
+    """k_tower_fwd / k_tower_bwd. Saved for the backward: x_0, the kernel's
+    mirrors a_1 .. a_L, and the transposed weight images packed by the
+    forward (the weights cannot change before the backward runs). The kernel
+    gives dx0 and dz_l; dW_l = dz_l^T a_{l-1}, db_l = sum_m dz_l and the
+    head's gradients are library ops here. When every parameter's .grad is
+    bound (the flat optimizer's views) they accumulate in place and autograd
+    gets None, as in _CrossNetFn."""
+
+    @staticmethod
+    def forward(ctx, x0, w_out, b_out, partial, save, bm, *wb):
+        ext = require_hip()
+        L = len(wb) // 2
+        weights = [w.contiguous() for w in wb[:L]]
+        biases = [b.contiguous() for b in wb[L:]]
+        M = x0.shape[0]
+        save = bool(save) and any(ctx.needs_input_grad)
+        acts = [torch.empty(M, w.shape[0], dtype=torch.bfloat16,
+                            device=x0.device) for w in weights] if save else []
+        out = torch.empty(M, dtype=torch.float32, device=x0.device)
+        wo = w_out.reshape(-1).contiguous()
+        bufs = _tower_images(weights, x0.shape[1], save, ext)
+        ext.tower_fwd(x0, weights[0].shape[1], bufs["w"], biases, acts, wo,
+                      b_out.reshape(-1).contiguous(),
+                      partial.contiguous() if partial is not None else None,
+                      out, bm)
+        if save:
+            ctx.save_for_backward(x0, wo, *acts)
+            ctx.bufs = bufs
+            ctx.bm = bm
+            ctx._params = (wb[:L], wb[L:], w_out, b_out)
+            ctx._has_partial = partial is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ext = require_hip()
+        x0, wo, *acts = ctx.saved_tensors
+        weights, biases, w_out, b_out = ctx._params
+        L, K0 = len(weights), weights[0].shape[1]
+        dout = g.contiguous().float()
+        dzs = [torch.empty_like(a) for a in acts]
+        dx0 = torch.empty_like(x0)
+        ext.tower_bwd(K0, acts, ctx.bufs["wt"], dout, wo, dzs, dx0, ctx.bm)
+        ins = [x0[:, :K0]] + acts[:-1]
+        params = (*weights, *biases, w_out, b_out)
+        prebound = all(p.is_leaf and p.requires_grad and p.grad is not None
+                       and p.grad.dtype == torch.bfloat16
+                       and p.grad.is_contiguous() for p in params)
+        dpart = dout if ctx._has_partial else None
+        dvec = dout.to(torch.bfloat16).unsqueeze(0)
+        if prebound:
+            for W, b, dz, a in zip(weights, biases, dzs, ins):
+                W.grad.addmm_(dz.t(), a)
+                b.grad.add_(dz.sum(0))
+            w_out.grad.view(1, -1).addmm_(dvec, acts[-1])
+            b_out.grad.add_(dout.sum().to(b_out.grad.dtype))
+            return (dx0, None, None, dpart, None, None) + (None,) * (2 * L)
+        need = ctx.needs_input_grad
+        dwo = (dvec @ acts[-1]).view_as(w_out) if need[1] else None
+        dbo = (dout.sum().to(b_out.dtype).view_as(b_out) if need[2]
+               else None)
+        dws = [dz.t() @ a if need[6 + l] else None
+               for l, (dz, a) in enumerate(zip(dzs, ins))]
+        dbs = [dz.sum(0) if need[6 + L + l] else None
+               for l, dz in enumerate(dzs)]
+        return (dx0, dwo, dbo, dpart, None, None, *dws, *dbs)
+
+
+def _tower_fits(x0, weights, biases, w_out, b_out, partial) -> bool:
+    """The limits the bindings check (they refuse everything else)."""
+    bf = torch.bfloat16
+    if not (_use_hip(x0) and x0.is_contiguous()
+            and all(t.dtype == bf and t.device == x0.device
+                    for t in (x0, *weights, *biases, w_out, b_out))):
+        return False
+    M, K0p = x0.shape
+    L = len(weights)
+    return (K0p == _ceil32(weights[0].shape[1]) and K0p <= 512
+            and 1 <= L <= 4
+            and all(w.shape[0] % 16 == 0 and 16 <= w.shape[0] <= 512
+                    for w in weights)
+            and M * 512 * (L + 1) < 2 ** 31 and x0.data_ptr() % 16 == 0
+            and (partial is None or (partial.dtype == torch.float32
+                                     and partial.device == x0.device)))
+
+
+def mlp_tower(x0: torch.Tensor, weights, biases, w_out: torch.Tensor,
+              b_out: torch.Tensor, partial: torch.Tensor = None,
+              bm: int = 0) -> torch.Tensor:
+    """MLP tower with a logit head, differentiable w.r.t. every tensor
+    argument.
+
+    x0 [M, K0], or [M, ceil32(K0)] with zero pad columns; weights[l]
+    [H_l, H_{l-1}] (H_0 = K0) stored like nn.Linear, biases[l] [H_l];
+    w_out [H_L] or [1, H_L], b_out [1]. Computes
+    a_l = relu(W_l a_{l-1} + b_l) and returns the fp32 logit [M]
+    = w_out . a_L + b_out (+ partial [M]).
+
+    GPU: one HIP launch each way (ops/csrc/tower.hip) for contiguous bf16
+    x0 [M, K0p], K0p = ceil32(K0) <= 512, bf16 parameters, 1 to 4 hidden
+    layers, every width a multiple of 16 in 16..512 and M*512*(L+1) < 2^31:
+    bf16 operands, fp32 arithmetic, each activation rounded to bf16 once.
+    Everything else, and the CPU, takes torch ops in the parameters' dtype.
+    ``bm`` forces the kernels' row tile (16 or 32; 0 = the launcher's
+    choice)."""
+    weights, biases = list(weights), list(biases)
+    ok = (x0.dim() == 2 and len(weights) == len(biases) >= 1
+          and all(w.dim() == 2 for w in weights))
+    if ok:
+        widths = [weights[0].shape[1]] + [w.shape[0] for w in weights]
+        ok = (all(w.shape[1] == k and b.shape == (w.shape[0],)
+                  for w, b, k in zip(weights, biases, widths))
+              and x0.shape[1] in (widths[0], _ceil32(widths[0]))
+              and tuple(w_out.shape) in ((widths[-1],), (1, widths[-1]))
+              and b_out.numel() == 1
+              and (partial is None or partial.shape == (x0.shape[0],)))
+    if not ok:
+        raise ValueError("mlp_tower takes x0 [M, K0 or ceil32(K0)], "
+                         "weights[l] [H_l, H_{l-1}] with biases[l] [H_l], "
+                         "w_out [H_L] or [1, H_L], b_out [1], partial [M]")
+    if (_TOWER and _tower_fits(x0, weights, biases, w_out, b_out, partial)
+            and require_hip() is not None):
+        return _TowerFn.apply(x0, w_out, b_out, partial,
+                              torch.is_grad_enabled(), bm, *weights, *biases)
+    return _tower_torch(x0, weights, biases, w_out, b_out, partial)
+
+
 # ----------------------------------------------------------------- fused loss
 
 class _FusedBCEFn(torch.autograd.Function):

@@ -26,6 +26,7 @@ ext = CUDAExtension(
         "openembedding_amd/ops/csrc/dlrm.hip",
         "openembedding_amd/ops/csrc/cross.hip",
         "openembedding_amd/ops/csrc/cross_lr.hip",
+        "openembedding_amd/ops/csrc/tower.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3"],
