@@ -150,6 +150,9 @@ void emb_tower_fwd(const TowerArgs*, const void*, long, long, long,
                    hipStream_t_);
 void emb_tower_bwd(const TowerArgs*, const float*, const void*, const void*,
                    void*, long, long, int, hipStream_t_);
+int emb_tower_wgrad_plan(const TowerWgradArgs*, int, long*);
+void emb_tower_wgrad(const TowerWgradArgs*, const TowerFoldArgs*,
+                     const float*, float*, int, hipStream_t_);
 void emb_mlp3_bias_bwd(const float*, const void*, const void*, const void*,
                        const void*, long, long, float*, void*, void*, void*,
                        void*, void*, int, int, int, hipStream_t_);
@@ -2548,6 +2551,105 @@ void tower_bwd(long K0, std::vector<torch::Tensor> acts,
                   (int)bm, cur_stream());
 }
 
+// the shapes of the wgrad's table, which is all its plan reads
+static TowerWgradArgs tower_wgrad_shapes(long M, long K0p,
+                                         const std::vector<long>& h) {
+    TowerWgradArgs a{};
+    a.L = (int)h.size();
+    a.M = (int)M;
+    a.hl = (int)h.back();
+    for (size_t l = 0; l < h.size(); ++l) {
+        a.ly[l].h = (int)h[l];
+        a.ly[l].jdim = (int)(l ? h[l - 1] : K0p);
+    }
+    return a;
+}
+
+// (S, floats): the M-slices tower_wgrad cuts M rows into for m_split
+// (0 = the launcher's rule) and the fp32 scratch it then needs
+std::tuple<long, long> tower_wgrad_plan(long M, long K0,
+                                        std::vector<long> widths,
+                                        long m_split) {
+    const char* who = "tower_wgrad_plan";
+    tower_check_shape(M, K0, ceil32(K0), widths, 0, who);
+    TORCH_CHECK(m_split >= 0 && m_split <= 16, who,
+                ": m_split must be in 0..16, got ", m_split);
+    const TowerWgradArgs a = tower_wgrad_shapes(M, ceil32(K0), widths);
+    long floats = 0;
+    const long S = emb_tower_wgrad_plan(&a, (int)m_split, &floats);
+    return {S, floats};
+}
+
+// Every parameter gradient from the mirrors: acts[l] and dzs[l] [M, H_{l+1}]
+// as tower_fwd and tower_bwd left them, dout fp32 [M]. grads: dW_1 .. dW_L
+// ([H_l, H_{l-1}], dW_1 [H_1, K0]), db_1 .. db_L, dw_out (H_L elements),
+// db_out (1), contiguous bf16; accumulate: grads += (fp32, one rounding),
+// else they are overwritten. scratch: fp32, tower_wgrad_plan's size at least.
+void tower_wgrad(torch::Tensor x0, long K0, std::vector<torch::Tensor> acts,
+                 std::vector<torch::Tensor> dzs, torch::Tensor dout,
+                 std::vector<torch::Tensor> grads, bool accumulate,
+                 torch::Tensor scratch, long m_split) {
+    const char* who = "tower_wgrad";
+    TORCH_CHECK(x0.is_cuda() && x0.scalar_type() == torch::kBFloat16, who,
+                ": x0 must be bf16 on a GPU");
+    TORCH_CHECK(x0.dim() == 2 && x0.is_contiguous()
+                && (reinterpret_cast<uintptr_t>(x0.data_ptr()) & 15) == 0,
+                who, ": x0 must be contiguous [M, K0p], 16-byte aligned");
+    const long M = x0.size(0), K0p = x0.size(1), L = (long)acts.size();
+    TORCH_CHECK(dzs.size() == acts.size()
+                && grads.size() == 2 * acts.size() + 2, who,
+                ": one dz per mirror and the gradients of W_1 .. W_L, "
+                "b_1 .. b_L, w_out, b_out");
+    std::vector<long> h;
+    for (const torch::Tensor& t : acts) {
+        TORCH_CHECK(t.dim() == 2, who, ": a mirror is [M, H_l]");
+        h.push_back(t.size(1));
+    }
+    tower_check_shape(M, K0, K0p, h, 0, who);
+    TORCH_CHECK(m_split >= 0 && m_split <= 16, who,
+                ": m_split must be in 0..16, got ", m_split);
+    TowerWgradArgs a = tower_wgrad_shapes(M, K0p, h);
+    TowerFoldArgs f{};
+    f.n = (int)(2 * L + 2);
+    f.K0 = (int)K0;
+    f.accumulate = accumulate ? 1 : 0;
+    for (long l = 0; l < L; ++l) {
+        tower_check_mat(acts[l], x0, M, h[l], "a mirror", who);
+        tower_check_mat(dzs[l], x0, M, h[l], "a dz", who);
+        a.ly[l].dz = dzs[l].data_ptr();
+        a.ly[l].a = l ? acts[l - 1].data_ptr() : x0.data_ptr();
+        const torch::Tensor& gw = grads[l];
+        const long cols = l ? h[l - 1] : K0;
+        TORCH_CHECK(gw.is_cuda() && gw.device() == x0.device()
+                    && gw.scalar_type() == torch::kBFloat16
+                    && gw.is_contiguous() && gw.dim() == 2
+                    && gw.size(0) == h[l] && gw.size(1) == cols, who,
+                    ": a weight gradient must be contiguous bf16 [", h[l],
+                    ", ", cols, "] on one GPU");
+        tower_check_vec(grads[L + l], x0, h[l], "a bias gradient", who);
+    }
+    a.al = acts[L - 1].data_ptr();
+    tower_check_vec(grads[2 * L], x0, h[L - 1], "the gradient of w_out", who);
+    tower_check_vec(grads[2 * L + 1], x0, 1, "the gradient of b_out", who);
+    for (long i = 0; i < 2 * L + 2; ++i) {
+        f.g[i].dst = grads[i].data_ptr();
+        f.g[i].vec =
+            (reinterpret_cast<uintptr_t>(grads[i].data_ptr()) & 15) == 0;
+    }
+    tower_check_f32(dout, x0, M, "dout", who);
+    long floats = 0;
+    emb_tower_wgrad_plan(&a, (int)m_split, &floats);
+    TORCH_CHECK(scratch.is_cuda() && scratch.device() == x0.device()
+                && scratch.scalar_type() == torch::kFloat32
+                && scratch.is_contiguous() && scratch.numel() >= floats
+                && (reinterpret_cast<uintptr_t>(scratch.data_ptr()) & 15) == 0,
+                who, ": scratch must be contiguous 16-byte-aligned fp32 with "
+                "at least ", floats, " elements (tower_wgrad_plan)");
+    const c10::cuda::CUDAGuard guard(x0.device());
+    emb_tower_wgrad(&a, &f, dout.data_ptr<float>(),
+                    scratch.data_ptr<float>(), (int)m_split, cur_stream());
+}
+
 long tower_bm(long M, long bm) { return emb_tower_bm(M, (int)bm); }
 
 // the k-split of a stage with n output columns over a contraction of k
@@ -3343,6 +3445,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("K0"), pybind11::arg("acts"), pybind11::arg("wtimgs"),
           pybind11::arg("dout"), pybind11::arg("w_out"), pybind11::arg("dzs"),
           pybind11::arg("dx0"), pybind11::arg("bm") = 0);
+    m.def("tower_wgrad", &tower_wgrad,
+          "MLP tower wgrad: dW_l, db_l, dw_out and db_out from the mirrors in "
+          "one MFMA launch and a fold, no atomics",
+          pybind11::arg("x0"), pybind11::arg("K0"), pybind11::arg("acts"),
+          pybind11::arg("dzs"), pybind11::arg("dout"), pybind11::arg("grads"),
+          pybind11::arg("accumulate"), pybind11::arg("scratch"),
+          pybind11::arg("m_split") = 0);
+    m.def("tower_wgrad_plan", &tower_wgrad_plan,
+          "(M-slices, fp32 scratch elements) of tower_wgrad for m_split",
+          pybind11::arg("M"), pybind11::arg("K0"), pybind11::arg("widths"),
+          pybind11::arg("m_split") = 0);
     m.def("tower_bm", &tower_bm,
           "rows per block the tower kernels' launcher picks for M rows",
           pybind11::arg("M"), pybind11::arg("bm") = 0);

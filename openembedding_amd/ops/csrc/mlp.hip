@@ -27,6 +27,7 @@
 #include "dense_tail.h"
 #include "flat_opt.h"
 #include "launch_common.h"
+#include "wgrad_common.h"
 
 typedef __hip_bfloat16 mbf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -744,30 +745,10 @@ extern "C" void emb_mlp3_bwd(const float* dout, long M, long K0p,
 // 16-column block is 32 B = 8 banks), so the transposed reads are
 // conflict-free per half; the b128 stores (8 lanes = one 128-B row, next
 // row 8 banks on) are too. Columns 64..79 are never read.
-
-#define WG_KC 128           // m-chunk staged per LDS round
-#define WG_LD 80            // LDS row stride (elements), see above
-
-// LDS row of logical chunk row r (see above)
-static __device__ __forceinline__ int wg_lds_row(int r) {
-    return (r & ~31) | ((r & 4) << 2) | ((r & 24) >> 1) | (r & 3);
-}
-
-// Transposed fragment read. Preconditions (ISA): every lane supplies an
-// in-bounds 8-byte-aligned address and EXEC is all ones — call it only
-// from block-uniform control flow.
-static __device__ __forceinline__ bf16x8 lds_tr_frag(const mbf16* p) {
-    union { s16x4 h[2]; bf16x8 v; } u;
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef __attribute__((address_space(3))) s16x4* lds_p;
-    u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)p);
-    u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (lds_p)(p + 16 * WG_LD));
-#else
-    u.h[0] = u.h[1] = s16x4{0, 0, 0, 0};
-#endif
-    return u.v;
-}
+//
+// WG_KC (the 128-row chunk), WG_LD, wg_lds_row (the permutation) and
+// lds_tr_frag (the transposed read) live in wgrad_common.h: tower.hip's
+// k_tower_wgrad takes the same path.
 
 extern "C" __global__ __launch_bounds__(512, 2)
 void k_mlp3_wgrad(const mbf16* __restrict__ dz1,   // [M, H]

@@ -23,8 +23,9 @@
 //   dz_1 .. dz_L are mirrored to HBM as [M, H_l]
 // No atomics: each element is written once, in one fixed order of sums, so
 // both kernels are bitwise reproducible. dW_l = dz_l^T a_{l-1}, db_l =
-// sum_m dz_l and the head's gradients are library ops on the mirrors
-// (ops/dispatch.py).
+// sum_m dz_l and the head's gradients come from the mirrors in one more
+// launch and a fold (k_tower_wgrad, k_tower_wgrad_fold, below), again without
+// atomics; ops/dispatch.py keeps library ops for a partly frozen tower.
 //
 // Both directions are chains of the same stage, out [BM, n] = tile [BM, 32
 // ks] x image^T: the forward with the images of W_l and the bias + ReLU
@@ -67,6 +68,7 @@
 
 #include "cross_common.h"
 #include "tower.h"
+#include "wgrad_common.h"
 
 #define TW_WAVES 8
 #define TW_LD 520            // a tile row: 512 + 8 bf16
@@ -348,6 +350,251 @@ void k_tower_bwd(const TowerArgs a,
     }
 }
 
+// ---- wgrad ------------------------------------------------------------
+// Every parameter gradient of the tower from the mirrors, two launches:
+//   dW_l[i,j] = sum_m dz_l[m,i] a_{l-1}[m,j]      db_l[i] = sum_m dz_l[m,i]
+//   dw_out[k] = sum_m dout[m] a_L[m,k]            db_out  = sum_m dout[m]
+// (a_0 = x0; fp32 products and sums, the head's product rounded once), then
+// grad = bf16(float(base) + s) or bf16(s): one rounding per gradient.
+//
+// k_tower_wgrad: grid (tiles + 1, S). blockIdx.x walks the 64 x 64 output
+// tiles of all layers (a layer narrower than 64 is one partial tile),
+// blockIdx.y is the M-slice, `cps` whole 128-row chunks. The data path is
+// k_mlp3_wgrad's (wgrad_common.h): both operands staged row-major with
+// 16-byte loads, rows permuted inside each 32-row step, transposed fragment
+// reads, the next chunk's loads in flight under the MFMAs. Wave w owns
+// subtiles {w, w + 8} of the 4 x 4 grid of 16 x 16; a subtile that lies
+// outside the matrix is skipped (wave-uniform). Blocks with tj == 0 also sum
+// the columns of the dz tile they staged (db_l). The block with blockIdx.x
+// == tiles is the slice's head role. Everything lands in the slice's slab of
+// the scratch with plain stores, each element written by one thread: no
+// atomics and nothing to zero. k_tower_wgrad_fold sums the slabs in the order
+// ((p0 + p1) + p2) + .. and rounds, so a tower's wgrad is bitwise
+// reproducible like its forward and backward.
+
+// The head role: column sums of dout[m] * a_L[m, :] and sum dout over the
+// slice. Thread (r, c) takes columns 8c .. 8c+7 of rows mbeg + r, + rg, ..;
+// the rg row groups meet in LDS [rg][hl + 1] and are added r = 0, 1, ...
+static __device__ __forceinline__ void tower_wgrad_head(
+        const uint16_t* __restrict__ al, const float* __restrict__ dout,
+        int hl, int mbeg, int mend, float* red, float* __restrict__ out) {
+    const int cg = hl >> 3;
+    int rg = 512 / cg;                   // rg (hl + 1) <= 4160 floats of LDS
+    if (rg > 64) rg = 64;
+    const int t = threadIdx.x, r = t / cg, c = t - r * cg;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ds = 0.f;
+    if (r < rg) {
+        for (int m = mbeg + r; m < mend; m += rg) {
+            const float dv = dout[m];
+            const uint4 v = *reinterpret_cast<const uint4*>(
+                __builtin_assume_aligned(al + m * hl + 8 * c, 16));
+            float lo[4], hi[4];
+            cross_unpack(make_uint2(v.x, v.y), lo);
+            cross_unpack(make_uint2(v.z, v.w), hi);
+            #pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                acc[e] = acc[e] + dv * lo[e];
+                acc[4 + e] = acc[4 + e] + dv * hi[e];
+            }
+            ds = ds + dv;
+        }
+        float* const pr = red + r * (hl + 1);
+        #pragma unroll
+        for (int e = 0; e < 8; ++e) pr[8 * c + e] = acc[e];
+        if (c == 0) pr[hl] = ds;
+    }
+    __syncthreads();
+    for (int k = t; k <= hl; k += 512) {
+        float s = red[k];
+        for (int q = 1; q < rg; ++q) s = s + red[q * (hl + 1) + k];
+        out[k] = s;
+    }
+}
+
+__global__ __launch_bounds__(512, 2)
+void k_tower_wgrad(const TowerWgradArgs a,
+                   const float* __restrict__ dout,      // [M]
+                   float* __restrict__ scratch) {       // [S][per]
+    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * WG_KC * WG_LD];
+    uint16_t* const ldsA = lds;
+    uint16_t* const ldsB = lds + WG_KC * WG_LD;
+    const int bt = (int)blockIdx.x;
+    const int mbeg = (int)blockIdx.y * a.cps * WG_KC;
+    const int mend = mbeg + a.cps * WG_KC < a.M ? mbeg + a.cps * WG_KC : a.M;
+    float* const slab = scratch + (size_t)blockIdx.y * a.per;
+
+    if (bt == a.tiles) {                 // block-uniform
+        tower_wgrad_head(static_cast<const uint16_t*>(a.al), dout, a.hl,
+                         mbeg, mend, reinterpret_cast<float*>(lds),
+                         slab + a.hoff);
+        return;
+    }
+
+    // block -> (layer, i-tile, j-tile)
+    TowerWgradLayer ly = a.ly[0];
+    #pragma unroll
+    for (int l = 1; l < TOWER_MAXL; ++l)
+        if (l < a.L && bt >= a.ly[l].tile0) ly = a.ly[l];
+    const int h = ly.h, jdim = ly.jdim;
+    const int ti = (bt - ly.tile0) / ly.tj, tj = bt - ly.tile0 - ti * ly.tj;
+    const int i0 = ti * 64, j0 = tj * 64;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+
+    // staging: thread t owns piece (t & 7) of rows (t >> 3) and (t >> 3) + 64
+    // of both operands. h and jdim are multiples of 16, so a 16-byte piece is
+    // inside or outside the matrix; outside pieces and rows >= mend are
+    // zeros, never read from memory.
+    const int srow = (int)threadIdx.x >> 3, scol = ((int)threadIdx.x & 7) * 8;
+    const bool okA = i0 + scol < h, okB = j0 + scol < jdim;
+    const uint16_t* gA = static_cast<const uint16_t*>(ly.dz) + i0 + scol;
+    const uint16_t* gB = static_cast<const uint16_t*>(ly.a) + j0 + scol;
+    uint4 ra[2], rb[2];
+    auto load_chunk = [&](int m0) {
+        #pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int m = m0 + srow + 64 * p;
+            ra[p] = make_uint4(0u, 0u, 0u, 0u);
+            rb[p] = make_uint4(0u, 0u, 0u, 0u);
+            if (m < mend) {
+                if (okA)
+                    ra[p] = *reinterpret_cast<const uint4*>(
+                        __builtin_assume_aligned(gA + m * h, 16));
+                if (okB)
+                    rb[p] = *reinterpret_cast<const uint4*>(
+                        __builtin_assume_aligned(gB + m * jdim, 16));
+            }
+        }
+    };
+
+    f32x4 acc[2];
+    acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int si = (wave >> 2) * 16, sj = (wave & 3) * 16;
+    // the wave's subtiles that hold any element of dW_l (wave-uniform)
+    const bool do0 = i0 + si < h && j0 + sj < jdim;
+    const bool do1 = do0 && i0 + si + 32 < h;
+    // lane 4q+p of a 16-lane group g addresses LDS row 4g+q, columns 4p..4p+3
+    const int toff = (4 * (lane >> 4) + ((lane & 15) >> 2)) * WG_LD
+                   + 4 * (lane & 3);
+    const bool rider = tj == 0;          // block-uniform
+    float bsum = 0.f;
+
+    load_chunk(mbeg);
+    for (int m0 = mbeg; m0 < mend; m0 += WG_KC) {
+        __syncthreads();                 // the previous chunk's reads are done
+        #pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int o = wg_lds_row(srow + 64 * p) * WG_LD + scol;
+            *reinterpret_cast<uint4*>(ldsA + o) = ra[p];
+            *reinterpret_cast<uint4*>(ldsB + o) = rb[p];
+        }
+        __syncthreads();
+        if (m0 + WG_KC < mend) load_chunk(m0 + WG_KC);
+        if (rider) {
+            // db_l rides along (k_mlp3_wgrad's rider): 8 threads per column,
+            // each every 8th row, a shuffle tree inside the 8-lane group,
+            // then chunk by chunk - a fixed order. Zeros were staged beyond
+            // mend and h.
+            const int cc = (int)threadIdx.x >> 3, sub = (int)threadIdx.x & 7;
+            float s = 0.f;
+            for (int mm = sub; mm < WG_KC; mm += 8)
+                s += cross_f32(ldsA[wg_lds_row(mm) * WG_LD + cc]);
+            s += __shfl_down(s, 4);
+            s += __shfl_down(s, 2);
+            s += __shfl_down(s, 1);
+            bsum = bsum + s;
+        }
+        if (do0) {
+            #pragma unroll
+            for (int ks = 0; ks < WG_KC; ks += 32) {
+                const bf16x8 bv = lds_tr_frag(ldsB + ks * WG_LD + toff + sj);
+                const bf16x8 a0 = lds_tr_frag(ldsA + ks * WG_LD + toff + si);
+                acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    a0, bv, acc[0], 0, 0, 0);
+                if (do1) {
+                    const bf16x8 a1 = lds_tr_frag(ldsA + ks * WG_LD + toff
+                                                  + si + 32);
+                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        a1, bv, acc[1], 0, 0, 0);
+                }
+            }
+        }
+    }
+    if (rider) {
+        const int cc = (int)threadIdx.x >> 3;
+        if ((threadIdx.x & 7) == 0 && i0 + cc < h)
+            slab[ly.boff + i0 + cc] = bsum;
+    }
+    // C row = the A operand's column i, C column = j
+    float* const out = slab + ly.off;
+    const int j = j0 + sj + (lane & 15);
+    #pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int i = i0 + si + 32 * t + (lane >> 4) * 4;
+        #pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (j < jdim && i + r < h) out[(i + r) * ly.ldo + j] = acc[t][r];
+    }
+}
+
+// One thread per piece of 8 consecutive columns of one gradient row: the S
+// partials in slab order, one rounding, 16-byte loads and stores where the
+// gradient allows them (vec), else element by element with 2-byte stores
+// (dW_1 with an odd K0, b_out). Columns at and beyond `cols` of a slab row,
+// x0's pad columns, are not read.
+__global__ __launch_bounds__(256)
+void k_tower_wgrad_fold(const TowerFoldArgs f,
+                        const float* __restrict__ scratch) {
+    const int p = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (p >= f.pieces) return;
+    TowerFoldOne g = f.g[0];
+    #pragma unroll
+    for (int i = 1; i < TOWER_FOLDN; ++i)
+        if (i < f.n && p >= f.g[i].p0) g = f.g[i];
+    const int ppr = (g.cols + 7) >> 3;
+    const int q = p - g.p0, row = q / ppr, col = (q - row * ppr) * 8;
+    const float* src = scratch + g.src + row * g.ld + col;
+    uint16_t* dst = static_cast<uint16_t*>(g.dst) + row * g.cols + col;
+    const int nv = g.cols - col < 8 ? g.cols - col : 8;
+    if (g.vec) {
+        f32x4 s0 = *reinterpret_cast<const f32x4*>(src);
+        f32x4 s1 = *reinterpret_cast<const f32x4*>(src + 4);
+        for (int s = 1; s < f.S; ++s) {
+            const float* ps = src + (size_t)s * f.per;
+            s0 = s0 + *reinterpret_cast<const f32x4*>(ps);
+            s1 = s1 + *reinterpret_cast<const f32x4*>(ps + 4);
+        }
+        if (f.accumulate) {
+            const uint4 b = *reinterpret_cast<const uint4*>(dst);
+            float lo[4], hi[4];
+            cross_unpack(make_uint2(b.x, b.y), lo);
+            cross_unpack(make_uint2(b.z, b.w), hi);
+            #pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                s0[e] = lo[e] + s0[e];
+                s1[e] = hi[e] + s1[e];
+            }
+        }
+        unsigned h0[4], h1[4];
+        #pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            h0[e] = cross_rne(s0[e]);
+            h1[e] = cross_rne(s1[e]);
+        }
+        const uint2 lo2 = cross_pack(h0), hi2 = cross_pack(h1);
+        *reinterpret_cast<uint4*>(dst) = make_uint4(lo2.x, lo2.y, hi2.x,
+                                                    hi2.y);
+        return;
+    }
+    for (int e = 0; e < nv; ++e) {
+        float s = src[e];
+        for (int k = 1; k < f.S; ++k) s = s + src[(size_t)k * f.per + e];
+        if (f.accumulate) s = cross_f32(dst[e]) + s;
+        dst[e] = (uint16_t)cross_rne(s);
+    }
+}
+
 // ---- launchers --------------------------------------------------------
 
 // Rows per block. As in cross.hip a block streams every weight image
@@ -431,6 +678,113 @@ void emb_tower_bwd(const TowerArgs* args, const float* dout,
     const int grid = (int)((M + bm - 1) / bm), block = 64 * TW_WAVES;
     CROSS_LAUNCH(k_tower_bwd, a, dout, (const uint16_t*)w_out,
                  (const uint16_t*)al, (uint16_t*)dzl, (int)nl, (int)M);
+}
+
+}  // extern "C"
+
+// The wgrad's tables: tiles, slab offsets and the M-slices. S (m_split; 0 =
+// the rule) is a function of M and the widths alone, not of the device, so
+// the bits of a gradient do not change between machines. Slices are whole
+// 128-row chunks, `cps` each; S is then ceil(chunks / cps), so no slice is
+// empty and the fold reads only what this launch wrote.
+// The rule: enough slices that tiles x S fills 256 CUs twice (2 blocks fit
+// a CU; the WDL tower over K0p = 256 has 32 + 32 + 8 + 2 = 74 tiles and gets
+// 7, (256, 128, 64) has 26), at most 8, and at least 4 chunks a slice. The
+// last two come from the table: measured on an MI355X, us for this kernel +
+// its fold (scripts/bench_tower.py --sweep, K0 = 247, median of 7 blocks of
+// 200; the blocks of a figure differ by at most 0.5), with the first form of
+// the rule (fill twice, at most 16) in the last column and its S:
+//   M     widths           S = 1     2      4      8     16    first rule
+//   1024  512-256-128-32   22.8   16.3   16.7   22.1   22.0*   16.7 (4)
+//   1024  256-128-64       22.4   15.8   14.9   18.3   18.3*   18.3 (8)
+//   2048  512-256-128-32   37.7   23.8   20.7   23.9   33.8    21.9 (6)
+//   2048  256-128-64       37.3   23.1   18.5   20.1   29.4    29.4 (16)
+//   4096  512-256-128-32   67.3   38.6   29.9   30.0   37.7    28.9 (7)
+//   4096  256-128-64       66.8   38.0   26.0   23.7   31.2    31.2 (16)
+//   8192  512-256-128-32  126.6   68.2   47.3   41.2   48.5    41.0 (7)
+//   8192  256-128-64      125.9   67.5   40.6   31.0   35.8    35.9 (16)
+// (* M = 1024 has 8 chunks, so 16 is 8.) 16 slices lose everywhere - the
+// fold reads every slab - and below 512 rows a slice the launch is mostly
+// the slabs' traffic, hence the two caps; the rule now picks 2, 4, 7, 7 and
+// 2, 4, 8, 8 slices down the two columns of towers.
+static int tower_wgrad_plan(TowerWgradArgs* a, int m_split) {
+    int tiles = 0, off = 0, boff = 0;
+    for (int l = 0; l < a->L; ++l) {
+        TowerWgradLayer* y = &a->ly[l];
+        y->ldo = (y->jdim + 31) / 32 * 32;
+        y->tj = (y->jdim + 63) / 64;
+        y->tile0 = tiles;
+        y->off = off;
+        tiles += (y->h + 63) / 64 * y->tj;
+        off += y->h * y->ldo;
+    }
+    for (int l = 0; l < a->L; ++l) {
+        a->ly[l].boff = off + boff;
+        boff += a->ly[l].h;
+    }
+    a->tiles = tiles;
+    a->hoff = off + boff;
+    a->per = (a->hoff + a->hl + 1 + 3) / 4 * 4;
+    const int nch = a->M > 0 ? (a->M + WG_KC - 1) / WG_KC : 1;
+    int s = m_split;
+    if (s <= 0) {
+        s = (2 * 256 + tiles - 1) / tiles;
+        if (s > 8) s = 8;
+        if (s > nch / 4) s = nch / 4;
+        if (s < 1) s = 1;
+    }
+    if (s > 16) s = 16;
+    if (s > nch) s = nch;
+    a->cps = (nch + s - 1) / s;
+    return (nch + a->cps - 1) / a->cps;
+}
+
+extern "C" {
+
+// -> S, the slices the launcher cuts M into, and through `floats` the size
+// of the scratch it needs (S slabs). Only the shapes of `args` are read.
+int emb_tower_wgrad_plan(const TowerWgradArgs* args, int m_split,
+                         long* floats) {
+    TowerWgradArgs a = *args;
+    const int S = tower_wgrad_plan(&a, m_split);
+    if (floats) *floats = (long)S * a.per;
+    return S;
+}
+
+void emb_tower_wgrad(const TowerWgradArgs* args, const TowerFoldArgs* fold,
+                     const float* dout, float* scratch, int m_split,
+                     hipStream_t stream) {
+    TowerWgradArgs a = *args;
+    TowerFoldArgs f = *fold;
+    const int S = tower_wgrad_plan(&a, m_split), L = a.L;
+    dim3 grid((unsigned)(a.tiles + 1), (unsigned)S);
+    k_tower_wgrad<<<grid, 512, 0, stream>>>(a, dout, scratch);
+
+    int pieces = 0;
+    for (int i = 0; i < f.n; ++i) {
+        TowerFoldOne* g = &f.g[i];
+        if (i < L) {
+            const TowerWgradLayer& y = a.ly[i];
+            g->src = y.off;
+            g->rows = y.h;
+            g->cols = i ? y.jdim : f.K0;
+            g->ld = y.ldo;
+        } else {
+            g->rows = 1;
+            g->ld = 0;
+            g->src = i < 2 * L ? a.ly[i - L].boff
+                               : i == 2 * L ? a.hoff : a.hoff + a.hl;
+            g->cols = i < 2 * L ? a.ly[i - L].h : i == 2 * L ? a.hl : 1;
+        }
+        g->vec = g->vec && g->cols % 8 == 0;
+        g->p0 = pieces;
+        pieces += g->rows * ((g->cols + 7) / 8);
+    }
+    f.S = S;
+    f.per = a.per;
+    f.pieces = pieces;
+    const int fgrid = (pieces + 255) / 256;
+    k_tower_wgrad_fold<<<fgrid, 256, 0, stream>>>(f, scratch);
 }
 
 }  // extern "C"

@@ -1012,6 +1012,8 @@ def cross_network_lr(x0: torch.Tensor, U: torch.Tensor, V: torch.Tensor,
 # in one launch each way; OEAMD_TOWER=0 keeps the torch route on the GPU in
 # the same build (A/B runs). Read once at import.
 _TOWER = os.environ.get("OEAMD_TOWER", "1") != "0"
+# OEAMD_TOWER_WGRAD=0 keeps the library wgrads behind k_tower_bwd
+_TOWER_WGRAD = os.environ.get("OEAMD_TOWER_WGRAD", "1") != "0"
 
 
 def _ceil32(v: int) -> int:
@@ -1055,14 +1057,33 @@ def _tower_images(weights, K0p: int, with_t: bool, ext):
     return bufs
 
 
+def _tower_wgrad_scratch(weights, M: int, ext):
+    """The fp32 slabs of k_tower_wgrad, beside ``_tower_bufs`` on the first
+    weight and keyed like them (plus M, which sets the slices): allocated on
+    the first call, so a captured step replays on the buffer its warm-up
+    made."""
+    W1 = weights[0]
+    key = (M, tuple(w.shape for w in weights), W1.device)
+    held = getattr(W1, "_tower_wgrad_buf", None)
+    if held is None or held[0] != key:
+        floats = ext.tower_wgrad_plan(M, W1.shape[1],
+                                      [w.shape[0] for w in weights], 0)[1]
+        held = (key, torch.empty(floats, dtype=torch.float32,
+                                 device=W1.device))
+        W1._tower_wgrad_buf = held
+    return held[1]
+
+
 class _TowerFn(torch.autograd.Function):
-    """k_tower_fwd / k_tower_bwd. Saved for the backward: x_0, the kernel's
-    mirrors a_1 .. a_L, and the transposed weight images packed by the
-    forward (the weights cannot change before the backward runs). The kernel
-    gives dx0 and dz_l; dW_l = dz_l^T a_{l-1}, db_l = sum_m dz_l and the
-    head's gradients are library ops here. When every parameter's .grad is
-    bound (the flat optimizer's views) they accumulate in place and autograd
-    gets None, as in _CrossNetFn."""
+    """k_tower_fwd / k_tower_bwd / k_tower_wgrad. Saved for the backward:
+    x_0, the kernel's mirrors a_1 .. a_L, and the transposed weight images
+    packed by the forward (the weights cannot change before the backward
+    runs). k_tower_bwd gives dx0 and dz_l. When every parameter needs a
+    gradient, k_tower_wgrad and its fold give dW_l = dz_l^T a_{l-1}, db_l =
+    sum_m dz_l and the head's gradients (OEAMD_TOWER_WGRAD=0: library ops, as
+    for a partly frozen tower). When every parameter's .grad is bound (the
+    flat optimizer's views) they accumulate in place and autograd gets None,
+    as in _CrossNetFn."""
 
     @staticmethod
     def forward(ctx, x0, w_out, b_out, partial, save, bm, *wb):
@@ -1105,6 +1126,18 @@ class _TowerFn(torch.autograd.Function):
                        and p.grad.dtype == torch.bfloat16
                        and p.grad.is_contiguous() for p in params)
         dpart = dout if ctx._has_partial else None
+        need = ctx.needs_input_grad
+        if _TOWER_WGRAD and all(need[1:3]) and all(need[6:]):
+            # k_tower_wgrad + fold: every parameter gradient in two launches,
+            # in place when every .grad is bound, else into fresh tensors
+            grads = ([p.grad for p in params] if prebound else
+                     [torch.empty(p.shape, dtype=torch.bfloat16,
+                                  device=x0.device) for p in params])
+            ext.tower_wgrad(x0, K0, acts, dzs, dout, grads, prebound,
+                            _tower_wgrad_scratch(weights, x0.shape[0], ext), 0)
+            if prebound:
+                return (dx0, None, None, dpart, None, None) + (None,) * (2 * L)
+            return (dx0, grads[-2], grads[-1], dpart, None, None, *grads[:-2])
         dvec = dout.to(torch.bfloat16).unsqueeze(0)
         if prebound:
             for W, b, dz, a in zip(weights, biases, dzs, ins):
@@ -1113,8 +1146,7 @@ class _TowerFn(torch.autograd.Function):
             w_out.grad.view(1, -1).addmm_(dvec, acts[-1])
             b_out.grad.add_(dout.sum().to(b_out.grad.dtype))
             return (dx0, None, None, dpart, None, None) + (None,) * (2 * L)
-        need = ctx.needs_input_grad
-        dwo = (dvec @ acts[-1]).view_as(w_out) if need[1] else None
+        dwo =(dvec @ acts[-1]).view_as(w_out) if need[1] else None
         dbo = (dout.sum().to(b_out.dtype).view_as(b_out) if need[2]
                else None)
         dws = [dz.t() @ a if need[6 + l] else None
@@ -1157,7 +1189,9 @@ def mlp_tower(x0: torch.Tensor, weights, biases, w_out: torch.Tensor,
     GPU: one HIP launch each way (ops/csrc/tower.hip) for contiguous bf16
     x0 [M, K0p], K0p = ceil32(K0) <= 512, bf16 parameters, 1 to 4 hidden
     layers, every width a multiple of 16 in 16..512 and M*512*(L+1) < 2^31:
-    bf16 operands, fp32 arithmetic, each activation rounded to bf16 once.
+    bf16 operands, fp32 arithmetic, each activation rounded to bf16 once;
+    the parameter gradients come from one more launch and a fold when every
+    parameter needs one (OEAMD_TOWER_WGRAD=0: library ops).
     Everything else, and the CPU, takes torch ops in the parameters' dtype.
     ``bm`` forces the kernels' row tile (16 or 32; 0 = the launcher's
     choice)."""
